@@ -1,12 +1,25 @@
 """Benchmark of the SPT hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--scene S|T|D|R]
+    python bench.py --gpus N --steps K --warmup W [--scene S|T|D|R] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one synthetic
 NAG batch already resident in HBM.  N > 1: one process per GPU (torchrun env),
 every rank owns a different scene of the same shape (scenes shard data
 parallel, "weak" scaling), the only collective is the gradient all-reduce of
 the model parameters (RCCL).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, settles, warms up, times the K steps and prints the line
+(`value`, `ms_per_step`, ...); the fields of the other legs stay null.  `--full`
+adds them: kernel timers inside the timed steps and the `roofline` object, the
+stand-alone north-star kernel, the f32-exact / bf16 / local-graph steps, the
+train-batch companion, the preprocessing leg and the CPU baselines.
+
+The last timed step starts from the model's parameters and buffers and the
+random generators as built (put back outside the timed time), so it computes
+the same thing in every run of the same arguments - float atomics in the
+backward would otherwise make every training step start from slightly
+different parameters; `--dump-outputs DIR` writes what that step computed
+(the loss and the flat gradient of a training step, the logits of an inference step).
 """
 import argparse
 import json
@@ -73,7 +86,19 @@ def parse():
     p.add_argument("--rebuild-csr", action="store_true",
                    help="worst case: ignore the NAG's stored level CSR (nag[i+1].sub) and rebuild every "
                         "CSR view with the device sort each step")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beyond the headline figure: per-kernel timers and the roofline "
+                        "object, the stand-alone north-star kernel, the collective's timing, the f32-exact / "
+                        "bf16 / local-graph steps, the train-batch companion, the preprocessing leg and the "
+                        "CPU baselines (the --no-* switches above skip single legs of it)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed to DIR/<name>.npy "
+                        "(float32 / float64, at most DUMP_LIMIT_BYTES in all: larger outputs as a fixed, "
+                        "seeded sample of their rows)")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
 
 
 # Relative sizes of the six S3DIS areas (points after the reference's voxelisation: Area 1-6 =
@@ -403,6 +428,87 @@ def _log(msg):
     print(f"[bench {time.perf_counter() - _T0:7.1f}s] {msg}", file=sys.stderr, flush=True)
 
 
+def snapshot_inputs(path):
+    """What a step computes from besides the batch: the model's parameters and buffers and the
+    host and device random generators (the iteration mode's chain samples with them).  The
+    optimizer state is not among them: it only enters the update after the loss and gradients."""
+    model = getattr(path, "model", None)
+    return {"model": ({k: v.detach().clone() for k, v in model.state_dict().items()}
+                      if model is not None else None),
+            "rng": torch.get_rng_state(),
+            "rng_cuda": torch.cuda.get_rng_state_all()}
+
+
+def restore_inputs(path, snap):
+    """Put the snapshot back IN PLACE (the same tensors: a captured graph keeps reading them)."""
+    model = getattr(path, "model", None)
+    if model is not None:
+        with torch.no_grad():
+            for k, v in model.state_dict().items():
+                v.copy_(snap["model"][k])
+    torch.set_rng_state(snap["rng"])
+    torch.cuda.set_rng_state_all(snap["rng_cuda"])
+
+
+DUMP_LIMIT_BYTES = 60 * 10 ** 6       # all files of --dump-outputs together (headers aside)
+
+
+def step_outputs(path, ret):
+    """name -> tensor: what ``path.step()`` computed.  A training step returns its loss and leaves
+    the gradient, which goes on as ONE flat vector (``grad_flat``: every parameter's gradient in
+    ``model.parameters()`` order, zeros where a parameter has none - the layout of
+    ``parallel.FlatGradAllReduce.pack``, what the all-reduce and the optimizer see); the inference
+    step returns the logits per level; the scatter chain its three gradients.  Not written: the
+    updated parameters (AdamW moves an element by about lr * g / (|g| + eps), which turns the
+    rounding of a near-zero gradient into a step of size lr), and no per-parameter files: several
+    gradients are zero by construction (a GraphNorm downstream removes any per-channel constant,
+    e.g. the attention's value biases), what they hold is the rounding of their sums alone."""
+    out = {}
+    if torch.is_tensor(ret):
+        out["loss"] = ret
+    elif isinstance(ret, (list, tuple)):
+        if getattr(path, "model", None) is None:          # the scatter chain (--stages scatter)
+            names = ["grad_x0", "grad_x1", "grad_pooled2"]
+        else:
+            names = [f"logits_{i}" for i in range(len(ret))]
+        out.update(zip(names, ret))
+    opt = getattr(path, "opt", None)
+    if opt is not None and torch.is_tensor(ret):
+        out["grad_flat"] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1)
+                                      for p in path.model.parameters() if p.requires_grad])
+    return out
+
+
+def write_outputs(arrays, out_dir, limit=DUMP_LIMIT_BYTES):
+    """``arrays`` (name -> tensor) -> ``out_dir/<name>.npy`` in float32 (float64 stays float64).
+    Together they stay within ``limit`` bytes: the smallest arrays are written whole, the ones
+    that do not fit their share of what is left keep a sample of their rows - the same rows in
+    every run (a generator seeded with 0, sorted indices)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    items = []
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t if t.dtype == torch.float64 else t.float()
+        items.append((name, t))
+    items.sort(key=lambda it: it[1].numel() * it[1].element_size())
+    left, written = limit, {}
+    for i, (name, t) in enumerate(items):
+        share = left // (len(items) - i)
+        nbytes = t.numel() * t.element_size()
+        if nbytes > share and t.dim() > 0:
+            row = nbytes // max(t.shape[0], 1)
+            keep = max(1, share // max(row, 1))
+            g = torch.Generator().manual_seed(0)
+            rows = torch.randperm(t.shape[0], generator=g)[:keep].sort().values
+            t = t.index_select(0, rows.to(t.device))
+            nbytes = t.numel() * t.element_size()
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.cpu().numpy())
+        written[name] = list(t.shape)
+        left -= nbytes
+    return written
+
+
 def main():
     args = parse()
     if args.train_batch_child:
@@ -467,7 +573,7 @@ def main():
         nag = make_nag(args.scene, seed=1234 + rank, device=dev, graph=args.graph, order=args.order,
                        scale=mix[rank])
     path = hotpath.build(nag, dev, world=world, stages=args.stages, mode=args.mode, model=args.model,
-                         kernel_timers=True)
+                         kernel_timers=args.full)
     if args.graph == "random" and args.order == "storage":
         # PMC captures (profiles/traffic.json) exist per (scene, net) of the default generator only
         # (keyed by dtype too: a bf16 line never prints traffic fractions off the f32 capture's bytes)
@@ -477,6 +583,8 @@ def main():
     # A process that is the first to touch a box's GPU runs its first seconds ~10 % slow (clock
     # ramp; measured: the same binary 74.6 ms/step in the first process of a fresh box, 67.3 in
     # the fifth): untimed steps until `--settle` seconds have passed, then the W warm-up steps.
+    # The last timed step runs on the model as built (see below): keep what it computes from.
+    fresh = snapshot_inputs(path)
     t_settle = time.perf_counter()
     while True:
         go = time.perf_counter() - t_settle < args.settle
@@ -514,18 +622,35 @@ def main():
         torch.cuda.synchronize()
 
     _log("warm-up done, timing")
+    # Every step of a training path updates the parameters the next one starts from, and float
+    # atomics in the backward make each update differ from run to run in its last bits; AdamW
+    # carries that on over the steps.  So that the last timed step computes the same thing in
+    # every run (and in every build: --dump-outputs), it starts from the parameters, buffers and
+    # generators as built, put back in place between two barriers outside the timed time.
     barrier()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         path.step()
     barrier()
     dt = time.perf_counter() - t0
+    restore_inputs(path, fresh)
+    del fresh
+    barrier()
+    t0 = time.perf_counter()
+    ret = path.step()
+    barrier()
+    dt += time.perf_counter() - t0
     _log(f"timed region done: {dt / args.steps * 1e3:.2f} ms per step")
     from superpoint_transformer_amd import parallel
     dt = parallel.max_over_ranks(dt, dev)
     # the adopted views' verdicts that are still on their way (a training loop's last batch:
     # csr.verify_adopted) - outside the timed region, raises on a stale `sub`
     _csr.verify_adopted(block=True)
+    if args.dump_outputs and rank == 0:
+        # before anything below steps the path again
+        written = write_outputs(step_outputs(path, ret), args.dump_outputs)
+        _log(f"{len(written)} outputs of the last timed step written to {args.dump_outputs}")
+    del ret
 
     n0 = nag.num_points[0]
     # iteration mode: what the chain left for the model to step on (raw points are `value`'s unit)
@@ -535,8 +660,9 @@ def main():
               for m in mix] if args.scene in SCENES else [n0] * world
     n0_all[rank] = n0
     value = sum(n0_all) * args.steps / dt / 1e6
-    roof = path.roofline(HBM_PEAK_GBS)
-    north_needed = roof.get("achieved") is None      # the step did not launch the stand-alone pool
+    # everything from here to the JSON line but the workload text is a --full leg
+    roof = path.roofline(HBM_PEAK_GBS) if args.full else None
+    north_needed = args.full and roof.get("achieved") is None  # the step did not launch the stand-alone pool
     workload = (path.describe(args.scene, SCENES.get(args.scene), args.graph)
                 if args.stages == "all" else path.describe(args.scene, SCENES.get(args.scene)))
     if args.order == "morton":
@@ -548,7 +674,7 @@ def main():
     # rank under SPT_FORCE_COLLECTIVES=1); null without a process group
     collective = None
     bucket = getattr(path, "bucket", None)
-    if bucket is not None and dist.is_initialized():
+    if args.full and bucket is not None and dist.is_initialized():
         bucket.pack()
         us = bucket.time_allreduce_us()
         collective = {"backend": dist.get_backend(), "ranks": dist.get_world_size(),
@@ -559,7 +685,7 @@ def main():
     # bf16 products per f32 product (~2^-17 relative per product: 17 of f32's 24 bits; every f32 parity bar holds): print what the
     # same step costs on the f32 matrix pipe everywhere next to it (untimed for `value`).
     exact_ms = None
-    if args.dtype == "f32" and world == 1 and args.mode == "train" and not args.no_f32_exact:
+    if args.full and args.dtype == "f32" and world == 1 and args.mode == "train" and not args.no_f32_exact:
         precision.set_matrix_precision("f32-exact")
         for _ in range(2):
             path.step()
@@ -573,7 +699,7 @@ def main():
     # ... and under the reference's other trainer setting (`precision: bf16`, BASELINE config #2's
     # wording): bf16 matrix operands + bf16 storage of the point MLP's layer outputs
     bf16_ms = None
-    if args.dtype == "f32" and world == 1 and args.mode == "train" and not args.no_f32_exact:
+    if args.full and args.dtype == "f32" and world == 1 and args.mode == "train" and not args.no_f32_exact:
         precision.set_matrix_precision("bf16")
         for _ in range(2):
             path.step()
@@ -589,11 +715,12 @@ def main():
     pre = None
     headline = (args.mode == "train" and args.model == "spt64" and args.stages == "all"
                 and args.dtype == "f32")
+    companions = args.full and headline          # the legs of the default configuration's full line
     # The headline graph is the no-locality stress case BY CHOICE.  Real superpoint graphs are
     # spatially local (src/transforms/graph.py:193-321 builds them by radius search): the same step
     # on the kNN-on-centroids graph with the level-1/2 nodes stored along a Morton curve, next to it.
     local = None
-    if (headline and world == 1 and not args.no_local and not args.no_f32_exact
+    if (companions and world == 1 and not args.no_local and not args.no_f32_exact
             and args.graph == "random" and args.order == "storage"):
         north = path.northstar(HBM_PEAK_GBS) if north_needed else None   # (before the second scene's memory)
         if north is not None:
@@ -628,15 +755,15 @@ def main():
         if north is not None:
             roof.update(north)
     train_batch = None
-    if headline and world == 1 and rank == 0 and not args.no_train_batch and args.scene == "S":
+    if companions and world == 1 and rank == 0 and not args.no_train_batch and args.scene == "S":
         del path
         path = None
         torch.cuda.empty_cache()
         train_batch = train_batch_leg(dev)
         _log(f"train-batch companion done: {train_batch.get('ms_per_step_T')} ms captured, "
              f"{train_batch.get('ms_per_step_T_eager')} eager, iteration {train_batch.get('ms_per_iteration_T')}")
-    if rank == 0 and world == 1 and not headline:
-        del path                      # other BASELINE configs: the GPU line only
+    if rank == 0 and world == 1 and not companions:
+        del path                      # other BASELINE configs and plain runs: the GPU line only
     elif rank == 0 and world == 1:
         if path is not None:
             del path

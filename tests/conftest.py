@@ -37,8 +37,48 @@ def _seed_global_rng():
 
 
 def load_golden(name):
-    d = np.load(os.path.join(GOLDEN, name))
-    return {k: d[k] for k in d.files}
+    """name -> {key: array}.  A fixture larger than a committed file may be is stored as
+    ``<stem>.part<i>.npz`` (tests/golden/split_golden.py): the parts are read in order and the
+    arrays cut along their first axis (``<key>::<j>``) are put back together."""
+    path = os.path.join(GOLDEN, name)
+    if os.path.exists(path):
+        d = np.load(path)
+        return {k: d[k] for k in d.files}
+    stem, out, cut = path[:-len(".npz")], {}, {}
+    i = 0
+    while os.path.exists(f"{stem}.part{i}.npz"):
+        with np.load(f"{stem}.part{i}.npz") as d:
+            for k in d.files:
+                key, _, j = k.partition("::")
+                if j:
+                    cut.setdefault(key, []).append((int(j), d[k]))
+                    out.setdefault(key, None)
+                else:
+                    out[key] = d[k]
+        i += 1
+    if i == 0:
+        raise FileNotFoundError(path)
+    for key, pieces in cut.items():
+        out[key] = np.concatenate([a for _, a in sorted(pieces, key=lambda p: p[0])])
+    return out
+
+
+def golden_file(name, tmp_dir):
+    """A non-npz fixture stored as ``<name>.xz.part<i>`` byte ranges: decompressed to
+    ``tmp_dir/<name>``, whose path is returned."""
+    import lzma
+    src = os.path.join(GOLDEN, name + ".xz")
+    data, i = b"", 0
+    while os.path.exists(f"{src}.part{i}"):
+        with open(f"{src}.part{i}", "rb") as f:
+            data += f.read()
+        i += 1
+    if i == 0:
+        raise FileNotFoundError(src)
+    out = os.path.join(str(tmp_dir), name)
+    with open(out, "wb") as f:
+        f.write(lzma.decompress(data))
+    return out
 
 
 def t64(a):

@@ -11,9 +11,11 @@ import numpy as np
 import pytest
 import torch
 
+from conftest import load_golden
+
 pytestmark = pytest.mark.gpu
 
-G = np.load(os.path.join(os.path.dirname(__file__), "golden", "attentive_pool.npz"))
+G = load_golden("attentive_pool.npz")
 
 
 def _close(a, ref, name):
@@ -38,7 +40,7 @@ def _make(tag):
 @pytest.mark.parametrize("tag", ["a", "b", "c"])
 def test_attentive_pool_matches_the_reference(tag, dev):
     pool = _make(tag)
-    state = {k[len(tag) + 5:]: torch.from_numpy(G[k]).float() for k in G.files
+    state = {k[len(tag) + 5:]: torch.from_numpy(G[k]).float() for k in G
              if k.startswith(tag + "__p__")}
     assert set(state) == set(dict(pool.named_parameters()))        # the reference's names
     pool.load_state_dict(state)
@@ -55,7 +57,7 @@ def test_attentive_pool_matches_the_reference(tag, dev):
     _close(y.detach(), t("out"), "out")
     _close(xc.grad, t("g_x_child"), "g_x_child")
     _close(ea.grad, t("g_edge_attr"), "g_edge_attr")
-    if f"{tag}__g_x_parent" in G.files:
+    if f"{tag}__g_x_parent" in G:
         _close(xp.grad, t("g_x_parent"), "g_x_parent")
     else:
         assert xp.grad is None                                      # learnt queries

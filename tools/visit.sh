@@ -4,7 +4,7 @@
 # legs:
 #   tests[:<pytest args>]  the -m gpu suite (or the given selection), summary + log
 #   smoke                  __graft_entry__.smoke()
-#   bench[:<bench args>]   the default bench line (or with the given arguments) -> <tag>_bench<suffix>.json
+#   bench[:<bench args>]   the full bench line (bench.py --full, plus the given arguments) -> <tag>_bench<suffix>.json
 #   configs                the other BASELINE configurations, one line each -> <tag>_bench_configs.jsonl
 #   stats:<S|T|L|128|bf16> rocprofv3 --kernel-trace of the train step -> <tag>_*_kernel_stats.csv
 #   pmc[:<bench args>]     FETCH_SIZE / WRITE_SIZE passes of the step (tools/pmc_step.sh)
@@ -31,7 +31,7 @@ for LEG in "$@"; do
     bench)
       SUF=$(echo "$ARG" | tr -c 'A-Za-z0-9\n' '_' | sed 's/__*/_/g; s/^_//; s/_$//')
       OUT=gpurun_out/${TAG}_bench${SUF:+_$SUF}.json
-      python bench.py $ARG 2> ${OUT%.json}.err | grep '^{"metric' > $OUT
+      python bench.py --full $ARG 2> ${OUT%.json}.err | grep '^{"metric' > $OUT
       python - "$OUT" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read())
