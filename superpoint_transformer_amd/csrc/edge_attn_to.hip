@@ -36,6 +36,8 @@ typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef short s16x8 __attribute__((ext_vector_type(8)));
+typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 constexpr int TE = 16;            // edges per tile
 constexpr int F = 32;             // in_rpe_dim
@@ -49,18 +51,21 @@ constexpr int IDS = 64;           // ints of a tile record: edge rows | targets 
 // LDS map, in floats.  Per wave:
 constexpr int L_G = 0;                         // [16 edges][16 chunks]: (qs | gout) of the edge's source, chunk ^ edge
 constexpr int L_GD = L_G + TE * 64;            // [16 edges][4 chunks]: (delta, ml) of the source, chunk + edge / 4
-constexpr int DT_LD = 36;                      // 32 words + 4: conflict-free both ways
-constexpr int L_DT = L_GD + TE * 16;           // [16 edges][DT_LD] words (hi << 16 | lo), one projection
-constexpr int L_TBL = L_DT + TE * DT_LD;       // rank[16], node[16]
+constexpr int L_DT = L_GD + TE * 16;           // [hi | lo][block][16 edges][16 o] bf16: D of one projection,
+                                               // 4-column chunk p of edge row r at position p ^ (r / 4) % 4
+constexpr int L_TBL = L_DT + 2 * NBW * TE * 8; // rank[16], node[16]
 constexpr int L_END = L_TBL + 32;
 // per pair of waves (the two head halves of one tile stream):
 constexpr int P_EA = 0;                        // 2 x [16][32] edge_attr rows (16-B chunks XOR-swizzled)
-constexpr int P_IDS = P_EA + 2 * TE * F;       // 4 slots of tile records
+constexpr int P_EB = P_EA + 2 * TE * F;        // 2 x [hi | lo][16][32] bf16: the rows split by the leader,
+                                               // 16-byte chunk ch of edge row r at position ch ^ ea_swz(r / 4)
+constexpr int P_IDS = P_EB + 2 * TE * F;       // 4 slots of tile records
 constexpr int P_MB = P_IDS + 4 * IDS;          // [64 lanes][8]: the leader's half of d edge_attr
 constexpr int P_GEA = P_MB + 512;              // [2][64 lanes][4]: what gedge_attr holds for the tile (accumulate)
 constexpr int P_FLAG = P_GEA + 512;            // hand-shake counters (F_*)
 constexpr int P_END = P_FLAG + 8;
-constexpr int F_EA = 0;       // leader -> follower: edge_attr rows of tile k and ids of tile k + 1 landed (k + 1)
+constexpr int F_EA = 0;       // leader -> follower: ids of tile 0 landed (1); edge_attr planes of tile k
+                              // written and ids of tile k + 1 landed (k + 2)
 constexpr int F_TOP = 1;      // follower -> leader: operands of tile k read (k + 1)
 constexpr int F_MB = 2;       // leader -> follower: mailbox holds tile k (k + 1)
 constexpr int F_MBFREE = 3;   // follower -> leader: mailbox of tile k consumed (k + 1)
@@ -84,14 +89,12 @@ constexpr int N_DQ = (SPT_TO_SKIP & 4) ? 0 : 2;   // dq stores per tile and wave
 constexpr int N_GATHER = (SPT_TO_SKIP & 8) ? 0 : 5;
 
 __device__ __forceinline__ void lds_dma16(const float* g, float* lds) {
-  const unsigned a = __builtin_amdgcn_readfirstlane(
-      (unsigned)(size_t)((__attribute__((address_space(3))) void*)lds));
+  const unsigned a = (unsigned)(size_t)((__attribute__((address_space(3))) void*)lds);
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off"
                :: "s"(a), "v"(g) : "memory");
 }
 __device__ __forceinline__ void lds_dma4(const void* g, float* lds) {
-  const unsigned a = __builtin_amdgcn_readfirstlane(
-      (unsigned)(size_t)((__attribute__((address_space(3))) void*)lds));
+  const unsigned a = (unsigned)(size_t)((__attribute__((address_space(3))) void*)lds);
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, off"
                :: "s"(a), "v"(g) : "memory");
 }
@@ -110,6 +113,7 @@ __device__ __forceinline__ void flag_set(lds_flag_t* f, int v) {
 }
 __device__ __forceinline__ void flag_wait(lds_flag_t* f, int v) {
   int spins = 0;
+#pragma clang loop unroll(disable)   // one copy of the poll: the wait is rarely more than one pass
   while (__builtin_amdgcn_readfirstlane(*f) < v) {
     __builtin_amdgcn_s_sleep(1);
     if (++spins > (1 << 22)) __builtin_trap();   // a lost partner: fail loudly, never hang the GPU
@@ -136,6 +140,11 @@ __device__ __forceinline__ float xg_sum(float v) {  // sum over the 4 lane group
   v += xor32(v);
   return v;
 }
+// the edge_attr planes' chunk swizzle per group of 4 rows, R = r / 4 -> 0, 2, 3, 1: the row reads
+// (ds_read_b128, lane (g, c): row c, chunk g) put the 16 lanes of each of their lane groups on distinct
+// banks, and the transposed reads (row 4 g + q, chunks 2 fb, 2 fb + 1) put rows r and r + 4 on the
+// two different halves of a 64-byte bank row
+__device__ __forceinline__ int ea_swz(int R) { return (0x1320 >> (4 * R)) & 3; }
 template <int NV, typename V>
 __device__ __forceinline__ void split_bf16(const float (&x)[NV], V& hi, V& lo) {
 #pragma unroll
@@ -531,39 +540,47 @@ __global__ __launch_bounds__(WAVES * 64, 2) void attn_bwd_to_kernel(
     int k = 0;                                    // tile index within the pair's range
     for (int64_t t = t_begin; t < t_end; t += t_step, ++k) {
       const int s0 = k & 3, s1 = (k + 1) & 3, s2 = (k + 2) & 3;   // id ring slots of tiles k, k+1, k+2
+      // edge_attr of tile k as hi / lo bf16 planes: split once per pair, by the leader, and read by
+      // both waves - rows (B operand of the recompute GEMM: lane (g, c) holds edge c, f = 8 g .. 8 g + 7)
+      // and transposed (B operand of dW: edges 4 g .. 4 g + 3 of f = 16 fb + c)
+      short* eb = reinterpret_cast<short*>(P + P_EB + (k & 1) * TE * F);
+      bf16x8 Ah, Al;
       if (leader) {
         // edge_attr rows of tile k and the ids of tile k + 1 have landed; behind them in the queue:
         // the dq rows of tile k - 1, the gathers of tile k, dk / dv atomics
         wait_vm<NDQ + NG>();
-        flag_set(flg + F_EA, k + 1);
-      } else {
-        flag_wait(flg + F_EA, k + 1);
-      }
-      const float* slab = P + P_EA + (k & 1) * TE * F;
-      bf16x8 Ah, Al;
-      {
+        const float* slab = P + P_EA + (k & 1) * TE * F;
         const float4 a0 = *reinterpret_cast<const float4*>(slab + c * F + (((2 * g) ^ (c & 7)) << 2));
         const float4 a1 = *reinterpret_cast<const float4*>(slab + c * F + (((2 * g + 1) ^ (c & 7)) << 2));
         const float a[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
         split_bf16<8>(a, Ah, Al);
+        short* w = eb + c * F + 8 * (g ^ ea_swz(c >> 2));
+        *reinterpret_cast<bf16x8*>(w) = Ah;
+        if constexpr (LO) *reinterpret_cast<bf16x8*>(w + TE * F) = Al;
+        flag_set(flg + F_EA, k + 2);
+      } else {
+        flag_wait(flg + F_EA, k + 2);
+        const short* r = eb + c * F + 8 * (g ^ ea_swz(c >> 2));
+        Ah = *reinterpret_cast<const bf16x8*>(r);
+        if constexpr (LO) Al = *reinterpret_cast<const bf16x8*>(r + TE * F);
       }
       s16x4 Eh[2], El[2];
+      {
+        // lane 4 q + x of group g: row 4 g + q, columns 16 fb + 4 x .. + 3 = half x % 2 of chunk 2 fb + x / 2
+        const int q = c >> 2, x = c & 3;
+        const short* er = eb + (4 * g + q) * F + 4 * (x & 1);
 #pragma unroll
-      for (int fb = 0; fb < 2; ++fb) {
-        float ev[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int e = 4 * g + i, f = 16 * fb + c;
-          ev[i] = slab[e * F + (((f >> 2) ^ (e & 7)) << 2) + (f & 3)];
+        for (int fb = 0; fb < 2; ++fb) {
+          const short* e2 = er + 8 * ((2 * fb + (x >> 1)) ^ ea_swz(g));
+          Eh[fb] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(__attribute__((address_space(3))) void*)e2);
+          if constexpr (LO)
+            El[fb] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+                (lds_s16x4*)(__attribute__((address_space(3))) void*)(e2 + TE * F));
         }
-        bf16x4 eh, el;
-        split_bf16<4>(ev, eh, el);
-        Eh[fb] = __builtin_bit_cast(s16x4, eh);
-        El[fb] = __builtin_bit_cast(s16x4, el);
       }
       const int* ids = ids_ring + s0 * IDS;
       const int t_c = ids[16 + c];                                    // target node of edge c
-      wait_lds();                                 // the edge_attr slab is consumed
+      wait_lds();                                 // the edge_attr planes are consumed
       // Both roles put exactly TWO requests behind the target rows (leader: the next tile's
       // edge_attr rows; follower of an accumulating call: what gedge_attr holds for this tile), so
       // that one counted wait serves both
@@ -720,8 +737,8 @@ __global__ __launch_bounds__(WAVES * 64, 2) void attn_bwd_to_kernel(
       wait_lds();                                 // the transposition buffer is free again
       issue_gather(s1);                           // records of tile k + 1 (its ids landed at the top)
 
-      // ---- per projection p (k, q, v): split D_p (B operand of d edge_attr^T += W_p^T D_p^T; one word
-      //      per value -> LDS), read back transposed (A operand of dW_p += D_p^T EA, and B operand of
+      // ---- per projection p (k, q, v): split D_p (B operand of d edge_attr^T += W_p^T D_p^T; hi / lo
+      //      bf16 planes -> LDS), read back transposed (A operand of dW_p += D_p^T EA, and B operand of
       //      the reduction per TARGET node of the tile on the matrix pipe: dk (p == 0) and dv (p == 2)
       //      of the nodes and, summed over the node rows, the bias gradient of every block) ---------
       f32x4 C2[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
@@ -735,8 +752,21 @@ __global__ __launch_bounds__(WAVES * 64, 2) void attn_bwd_to_kernel(
 #pragma unroll
         for (int i = 0; i < 4; ++i) S[i] = rk4[i] == c ? (short)0x3F80 : (short)0;
       }
-      unsigned* dtw = reinterpret_cast<unsigned*>(L + L_DT) + c * DT_LD + 4 * g;
-      const unsigned* dtr = reinterpret_cast<const unsigned*>(L + L_DT) + (4 * g) * DT_LD + c;
+      // D through LDS as bf16 planes: each lane writes its 4 consecutive o of edge c per block and
+      // plane (8 bytes; the XOR puts the 16 lanes of a write group on 16 distinct bank pairs), the
+      // transposed read returns edge rows 4 g .. 4 g + 3 of column o = c (lane 4 q + r of group g
+      // addresses row 4 g + q, chunk r: one 256-byte span per 32-lane half, conflict-free)
+      short* dtw = reinterpret_cast<short*>(L + L_DT) + c * 16 + 4 * (g ^ (c >> 2));
+      const short* dtr = reinterpret_cast<const short*>(L + L_DT) + (4 * g + (c >> 2)) * 16 + 4 * ((c & 3) ^ g);
+      auto tr_read = [&](int off) {
+        return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+            (lds_s16x4*)(__attribute__((address_space(3))) void*)(dtr + off));
+      };
+      const s16x8 SS = __builtin_shufflevector(S, S, 0, 1, 2, 3, 4, 5, 6, 7);
+      bf16x8 EE[2];                               // [Eh | El]: K-concatenated with [Tl | Th] below
+#pragma unroll
+      for (int fb = 0; fb < 2; ++fb)
+        EE[fb] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(Eh[fb], El[fb], 0, 1, 2, 3, 4, 5, 6, 7));
 #pragma unroll
       for (int p = 0; p < 3; ++p) {
         {
@@ -744,17 +774,20 @@ __global__ __launch_bounds__(WAVES * 64, 2) void attn_bwd_to_kernel(
 #pragma unroll
           for (int bl = 0; bl < NBW; ++bl) {
             const f32x4& X = p == 0 ? Ck[bl] : (p == 1 ? Cq[bl] : Cv[bl]);
-            u32x4 w;
 #pragma unroll
             for (int d = 0; d < 4; ++d) {
               const __bf16 h = (__bf16)X[d];
-              const __bf16 l = (__bf16)(X[d] - (float)h);
               Dh[4 * bl + d] = h;
-              Dl[4 * bl + d] = l;
-              w[d] = ((unsigned)__builtin_bit_cast(unsigned short, h) << 16) |
-                     (unsigned)__builtin_bit_cast(unsigned short, l);
+              if constexpr (LO) Dl[4 * bl + d] = (__bf16)(X[d] - (float)h);
             }
-            *reinterpret_cast<u32x4*>(dtw + 16 * bl) = w;
+          }
+          const s16x8 Dh16 = __builtin_bit_cast(s16x8, Dh);
+          *reinterpret_cast<s16x4*>(dtw) = __builtin_shufflevector(Dh16, Dh16, 0, 1, 2, 3);
+          *reinterpret_cast<s16x4*>(dtw + TE * 16) = __builtin_shufflevector(Dh16, Dh16, 4, 5, 6, 7);
+          if constexpr (LO) {
+            const s16x8 Dl16 = __builtin_bit_cast(s16x8, Dl);
+            *reinterpret_cast<s16x4*>(dtw + NBW * TE * 16) = __builtin_shufflevector(Dl16, Dl16, 0, 1, 2, 3);
+            *reinterpret_cast<s16x4*>(dtw + (NBW + 1) * TE * 16) = __builtin_shufflevector(Dl16, Dl16, 4, 5, 6, 7);
           }
 #pragma unroll
           for (int fb = 0; fb < 2; ++fb) {
@@ -769,24 +802,26 @@ __global__ __launch_bounds__(WAVES * 64, 2) void attn_bwd_to_kernel(
 #pragma unroll
         for (int bl = 0; bl < NBW; ++bl) {
           const int q6 = NBW * p + bl;
-          unsigned w[4];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) w[i] = dtr[i * DT_LD + 16 * bl];
-          const s16x4 Th = __builtin_bit_cast(s16x4, (u32x2){__builtin_amdgcn_perm(w[1], w[0], 0x07060302u),
-                                                             __builtin_amdgcn_perm(w[3], w[2], 0x07060302u)});
-          const s16x4 Tl = __builtin_bit_cast(s16x4, (u32x2){__builtin_amdgcn_perm(w[1], w[0], 0x05040100u),
-                                                             __builtin_amdgcn_perm(w[3], w[2], 0x05040100u)});
-#pragma unroll
-          for (int fb = 0; fb < 2; ++fb) {
-            if constexpr (LO) {
-              C3[q6][fb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(Tl, Eh[fb], C3[q6][fb], 0, 0, 0);
-              C3[q6][fb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(Th, El[fb], C3[q6][fb], 0, 0, 0);
-            }
-            C3[q6][fb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(Th, Eh[fb], C3[q6][fb], 0, 0, 0);
-          }
+          const s16x4 Th = tr_read(bl * TE * 16);
           f32x4 Cs = (f32x4){0.f, 0.f, 0.f, 0.f};
-          if constexpr (LO) Cs = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(S, Tl, Cs, 0, 0, 0);
-          Cs = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(S, Th, Cs, 0, 0, 0);
+          if constexpr (LO) {
+            // K-concatenation: lane l holds k = 8 (l / 16) + j of a 16x16x32 operand, so the halves
+            // j < 4 and j >= 4 are two 16x16x16 fragments (k = 4 (l / 16) + j) and ONE product sums
+            // both: C3 += Tl Eh + Th El (+ Th Eh, K = 16), Cs = S Tl + S Th
+            const s16x4 Tl = tr_read((NBW + bl) * TE * 16);
+            const bf16x8 TT = __builtin_bit_cast(bf16x8, __builtin_shufflevector(Tl, Th, 0, 1, 2, 3, 4, 5, 6, 7));
+#pragma unroll
+            for (int fb = 0; fb < 2; ++fb) {
+              C3[q6][fb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(TT, EE[fb], C3[q6][fb], 0, 0, 0);
+              C3[q6][fb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(Th, Eh[fb], C3[q6][fb], 0, 0, 0);
+            }
+            Cs = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, SS), TT, Cs, 0, 0, 0);
+          } else {
+#pragma unroll
+            for (int fb = 0; fb < 2; ++fb)
+              C3[q6][fb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(Th, Eh[fb], C3[q6][fb], 0, 0, 0);
+            Cs = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(S, Th, Cs, 0, 0, 0);
+          }
           gb[q6] += (Cs[0] + Cs[1]) + (Cs[2] + Cs[3]);        // rows >= nn are 0
           if (p == 0) CnK[bl] = Cs;
           if (p == 2) CnV[bl] = Cs;
