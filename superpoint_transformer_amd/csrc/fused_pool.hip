@@ -777,22 +777,68 @@ __global__ __launch_bounds__(256) void pool_bwd_gw_dense_kernel(
 }
 
 // ---- backward, main kernel ------------------------------------------------------------------------
-// Tiles walk the rows in the pool's CSR order.  S tile (f32, LDS) = gm where the winner's CSR
-// position is this row, else 0: the tile is zero-filled and the (gm, argpos) rows of the segments
-// it touches - one or two at 35 rows per segment - are SCATTERED into it (a lane owns N / 64
-// channels; no search, no compare per (row, channel)).  gW += S^T y_prev (16x16x16, contraction =
-// the tile's rows), gy = S W + y_prev M + c0 (16x16x32, W^T and M as split-bf16 rows in LDS), then
-// - as every fused layer's backward - the rows leave as the gradient of the previous layer's
-// normalised output and the two sums its GraphNorm backward needs (sum g', sum g' o') fall out of
-// the same registers.  The gathered x rows of the NEXT tile are requested before this tile's
-// GEMMs (one HBM round trip per tile, under the arithmetic).
+// Tiles walk the rows in the pool's CSR order.  S tile = gm where the winner's CSR position is this
+// row, else 0.  gW += S^T y_prev (contraction = the tile's 16 rows), gy = S W + y_prev M + c0
+// (16x16x32, W^T and M as split-bf16 rows in LDS), then - as every fused layer's backward - the rows
+// leave as the gradient of the previous layer's normalised output and the two sums its GraphNorm
+// backward needs (sum g', sum g' o') fall out of the same registers.  The gathered x rows of the
+// NEXT tile are requested before this tile's GEMMs (one HBM round trip per tile, under the
+// arithmetic).
 // WAVE PAIRS: the 128 x 64 weight-gradient accumulators are 128 registers per lane - with them a
-// wave has no room for the next tile's rows in flight and spills (measured: 78 % of the wave
-// cycles parked on memory).  Two waves of a pair therefore walk the SAME tiles: each stages the
-// tile into its own LDS buffers (the second read of a row is an L2 hit; no hand-shake between
-// the two is needed) and owns HALF of the output - the gW rows of N / 2 channels and K / 2 columns
-// of gy.  Per wave: 64 + 8 accumulators, ~150 registers, nothing spilled.
-// LO: split operands (hi + lo, 3 products);  X16: xprev holds bf16 values.
+// wave has no room for the next tile's rows in flight and spills.  Two waves of a pair therefore
+// walk the SAME tiles and each owns HALF of the output - the gW rows of N / 2 channels and K / 2
+// columns of gy.
+// ONE STAGED TILE PER PAIR, every operand formatted ONCE: wave hf of the pair gathers the tile rows
+// 8 hf .. 8 hf + 7 and scatters the winners of the channels hf N / 2 .. + N / 2 - 1; the pair's tile
+// record in LDS holds
+//   the raw x rows (f32; the epilogue's o = x - am),
+//   y_prev = leaky((x - am) sc + bs) as bf16 hi / lo planes [16][K] (rows >= cnt zero),
+//   S as bf16 hi / lo planes [16][N]: zero-filled, then only the winners are split and stored
+//   (one value per lane and segment, one or two segments per tile at 35 rows per segment).
+// Both waves read the planes as rows (`ds_read_b128`: the A operands of S W and y_prev M) and
+// transposed (`ds_read_b64_tr_b16`: both operands of S^T y_prev).  16-byte chunk ch of plane row r
+// sits at position ch ^ pl_swz(r): with it the 8 rows a 32-lane half of a transposed read touches
+// and the 16 rows of a lane group of the row read cover all 64 banks once (rows of 256, 128 and
+// 64 bytes).  The two waves hand over through four LDS counters per pair: F_STAGED + hf (tile k's
+// half is written: k + 1) and F_DONE + hf (tile k's planes are read: k + 1).
+// LO (split operands): C3 += sl Xh + sh Xl + sh Xh is one 16x16x32 product [sl | sh] [Xh | Xl] -
+// lane l holds k = 8 (l / 16) + j of a 16x16x32 operand and k = 4 (l / 16) + j of a 16x16x16 one, so
+// two fragments side by side in a lane are the K-concatenation - plus one 16x16x16 product sh Xh.
+// X16: xprev holds bf16 values.
+typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+typedef __attribute__((address_space(3))) volatile int lds_flag_t;   // ds_read / ds_write, never flat
+__device__ __forceinline__ void flag_set(lds_flag_t* f, int v) {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's LDS traffic so far has completed
+  *f = v;
+}
+// false: the partner never arrived.  The caller traps once it has left its tile loop - a trap inside
+// the poll gives that loop a second way to its back edge, with other memory operations in flight,
+// and the compiler then drains every count (`s_waitcnt vmcnt(0)`) at the end of each tile
+__device__ __forceinline__ bool flag_wait(lds_flag_t* f, int v) {
+  int spins = 0;
+  bool ok = true;
+#pragma clang loop unroll(disable)   // one copy of the poll: the wait is rarely more than one pass
+  while (__builtin_amdgcn_readfirstlane(*f) < v) {
+    __builtin_amdgcn_s_sleep(1);
+    if (++spins > (1 << 22)) {       // a lost partner: fail loudly, never hang the GPU
+      ok = false;
+      break;
+    }
+  }
+  asm volatile("" ::: "memory");
+  return ok;
+}
+// element offset of (row, col) in a [16][C] bf16 plane whose 16-byte chunks are XOR-swizzled
+template <int C>
+__device__ __forceinline__ int pl_off(int row, int col) {
+  constexpr int RPL = 128 / C;                   // plane rows per 256 bytes (all 64 banks)
+  static_assert(C == 32 || C == 64 || C == 128, "plane row of 64, 128 or 256 bytes");
+  const int swz = ((row / RPL) & (8 / RPL - 1)) << 1;
+  return row * C + ((((col >> 3) ^ swz) << 3) | (col & 7));
+}
+__device__ __forceinline__ s16x4 tr_read(const __bf16* p) {
+  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(__attribute__((address_space(3))) void*)p);
+}
 template <int K, int N, bool LO, bool X16, int NW>
 __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_pool_kernel(
     const float* __restrict__ gm, const int32_t* __restrict__ argpos,
@@ -804,13 +850,28 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_pool_kernel(
     FmlpRuns rt) {
   constexpr int KB = K / 16, NBK = N / 16, NS = N / 32, KS = K / 32;
   constexpr int NBH = NBK / 2, KBH = KB / 2;             // a wave's half of the outputs
-  constexpr int LDG = N + 4, LDX = K + 4;
+  constexpr int LDX = K + 4;
   constexpr int LDT = N + SPT_FPOOL_WPAD, LDM = K + SPT_FPOOL_WPAD;   // = 16 (mod 32): see fwd_pool_kernel's LDW
   static_assert((LDT % 32 == 16 && LDM % 32 == 16) || SPT_FPOOL_WPAD != 16, "conflict-free B fragments");
-  constexpr int CPL = N / 64;                            // channels a lane scatters per segment
   static_assert(K % 32 == 0 && N % 64 == 0 && NW % 2 == 0, "shape");
-  __shared__ __attribute__((aligned(16))) float g_lds[NW][TR * LDG];   // S tile
-  __shared__ __attribute__((aligned(16))) float x_lds[NW][TR * LDX];   // RAW xprev tile
+  constexpr int NP = NW / 2, NPL = LO ? 2 : 1;           // wave pairs; bf16 planes per operand
+  constexpr int HR = TR / 2;                             // tile rows a wave gathers
+  constexpr int CH = K / 4, NIT = HR * CH / 64;          // 4-value chunks per row, per lane
+  static_assert(HR * CH % 64 == 0, "whole waves of chunks");
+  constexpr int NH = N / 2;                              // channels a wave scatters: one per lane
+  static_assert(NH <= 64 && (NH & (NH - 1)) == 0, "one channel per lane");
+  constexpr int NZ = TR * (NH / 8) / 64;                 // 16-byte chunks a lane zero-fills per S plane
+  static_assert(TR * (NH / 8) % 64 == 0, "whole waves of chunks");
+  // the pair's tile record (bytes)
+  constexpr int T_X = 0;                                 // f32 [TR][LDX]: RAW xprev rows
+  constexpr int T_Y = T_X + TR * LDX * 4;                // bf16 [NPL][TR][K]: y_prev hi | lo
+  constexpr int T_S = T_Y + NPL * TR * K * 2;            // bf16 [NPL][TR][N]: S hi | lo
+  constexpr int T_PAD = T_S + NPL * TR * N * 2;          // where a scatter without a winner in the tile goes
+  constexpr int T_FLAG = T_PAD + 16;                     // hand-shake counters
+  constexpr int T_END = T_FLAG + 16;
+  static_assert(T_Y % 16 == 0 && T_END % 16 == 0, "16-byte chunks");
+  constexpr int F_STAGED = 0, F_DONE = 2;
+  __shared__ __attribute__((aligned(16))) unsigned char tile_lds[NP * T_END];
   __shared__ __attribute__((aligned(16))) __bf16 wt_hi[K * LDT];       // wt[k][n] = W[n][k]
   __shared__ __attribute__((aligned(16))) __bf16 wt_lo[LO ? K * LDT : 8];
   __shared__ __attribute__((aligned(16))) __bf16 mt_hi[K * LDM];       // mt[k][j] = M[j][k] (= M[k][j])
@@ -819,7 +880,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_pool_kernel(
   __shared__ __attribute__((aligned(16))) float c0l[K];
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int hf = wid & 1;                                // which half of the outputs
+  const int hf = wid & 1;                                // which half of the outputs, of the staging
   const int nb0 = hf * NBH, kb0 = hf * KBH;
   const int g = lane >> 4, c = lane & 15;
   const int run = blockIdx.y, gph = rt.g[run];
@@ -835,8 +896,12 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_pool_kernel(
                       (size_t)run * gridDim.x * (NW / 2) * 2 * SCR;
   gw_partial += (size_t)run * gridDim.x * N * K;
   pstat_partial += (size_t)run * gridDim.x * (NW / 2) * (2 * K + 1);
-  float* gl = g_lds[wid];
-  float* xl = x_lds[wid];
+  unsigned char* tl = tile_lds + (wid >> 1) * T_END;
+  float* xr = reinterpret_cast<float*>(tl + T_X);
+  __bf16* yp = reinterpret_cast<__bf16*>(tl + T_Y);      // lo plane: + TR K
+  __bf16* sp = reinterpret_cast<__bf16*>(tl + T_S);      // lo plane: + TR N
+  __bf16* pad = reinterpret_cast<__bf16*>(tl + T_PAD);
+  lds_flag_t* flg = (lds_flag_t*)(__attribute__((address_space(3))) void*)(tl + T_FLAG);
   for (int i = threadIdx.x; i < K * N; i += NW * 64) {
     const int k = i / N, n = i - k * N;
     const float w = W[(size_t)n * K + k];
@@ -857,6 +922,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_pool_kernel(
     pt[2 * K + i] = pbs[i];
     c0l[i] = c0g[i];
   }
+  if (lane < 4) flg[lane] = 0;                  // (both waves of the pair: the same value)
   __syncthreads();
 
   f32x4 C3[NBH][KB];       // C3[j][kb][r] = gW[16 (nb0 + j) + 4 g + r][16 kb + c]
@@ -884,38 +950,47 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_pool_kernel(
     rid = perm ? perm[q] : (int)q;
     sg = pos_seg[q];
   };
-  // (gm, argpos) of the lane's CPL channels of segment sgm
-  auto load_seg = [&](int sgm, int (&ap)[CPL], float (&gv)[CPL]) {
-    const size_t o = (size_t)sgm * N + CPL * lane;
-    if constexpr (CPL == 2) {
-      const int2 a2 = *reinterpret_cast<const int2*>(argpos + o);
-      const float2 g2 = *reinterpret_cast<const float2*>(gm + o);
-      ap[0] = a2.x; ap[1] = a2.y;
-      gv[0] = g2.x; gv[1] = g2.y;
-    } else {
-      ap[0] = argpos[o];
-      gv[0] = gm[o];
+  // this wave's HR rows of the tile (ids of the 16 rows in lanes 0 .. 15 of rid): one request per
+  // pair and row - unconditional, as load_rows
+  auto load_half = [&](int rid, typename RowChunk<X16>::type (&v)[NIT]) {
+#pragma unroll
+    for (int j = 0; j < NIT; ++j) {
+      const int q = lane + 64 * j, rl = q / CH, k = (q - rl * CH) << 2;
+      const int64_t xrow = (int64_t)__shfl(rid, HR * hf + rl, 64);
+      if constexpr (X16)
+        v[j] = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(xprev) + xrow * K + k);
+      else
+        v[j] = *reinterpret_cast<const float4*>(xprev + xrow * K + k);
     }
   };
-  // winners of one segment whose tile rows are [lo, hi): S[row][channel] = gm.  Branch-free: a
-  // lane whose winner lies outside writes a pad column of row 0 instead (never read)
-  auto scatter = [&](const int (&ap)[CPL], const float (&gv)[CPL], int row0i, int lo, int hi) {
-#pragma unroll
-    for (int q = 0; q < CPL; ++q) {
-      const int rr = ap[q] - row0i;
-      const bool ok = rr >= lo && rr < hi;
-      gl[ok ? rr * LDG + CPL * lane + q : N + q] = gv[q];
-    }
+  // (gm, argpos) of the lane's channel of segment sgm (N = 64: lanes 32 .. 63 repeat 0 .. 31 and
+  // never store)
+  const int chn = hf * NH + (lane & (NH - 1));
+  const bool sc_on = lane < NH;
+  auto load_seg = [&](int sgm, int& ap, float& gv) {
+    const size_t o = (size_t)sgm * N + chn;
+    ap = argpos[o];
+    gv = gm[o];
+  };
+  // the winner of one segment whose tile rows are [lo, hi): S[row][channel] = gm, split here.
+  // Branch-free: a lane whose winner lies outside writes the pad instead (never read)
+  auto scatter = [&](int ap, float gv, int row0i, int lo, int hi) {
+    const int rr = ap - row0i;
+    const bool ok = sc_on && rr >= lo && rr < hi;
+    const int o = pl_off<N>(rr & (TR - 1), chn);
+    const __bf16 h = (__bf16)gv;
+    *(ok ? sp + o : pad) = h;
+    if constexpr (LO) *(ok ? sp + TR * N + o : pad + 1) = (__bf16)(gv - (float)h);
   };
   if (ntiles > 0) {                             // (an empty run still writes its zero records below)
   int rid_l, seg_l, rid_n, seg_n;
   load_ids(pair, rid_l, seg_l);
-  typename RowChunk<X16>::type xv[TR * (K / 4) / 64];   // raw rows of the tile about to be staged
-  load_rows<K, X16>(xprev, rid_l, xv, lane);
+  typename RowChunk<X16>::type xv[NIT];         // raw rows of the tile about to be staged
+  load_half(rid_l, xv);
   // the tile's FIRST and LAST segment (at 35 rows per segment a tile touches one or two): their
   // (gm, argpos) rows travel a tile ahead like the x rows; further segments are fetched in place
-  int apA[CPL], apB[CPL];
-  float gvA[CPL], gvB[CPL];
+  int apA, apB;
+  float gvA, gvB;
   {
     const int c0 = cnt_of(pair < ntiles ? pair : ntiles - 1);
     load_seg(__builtin_amdgcn_readlane(seg_l, 0), apA, gvA);
@@ -933,6 +1008,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_pool_kernel(
 #pragma unroll
     for (int i = 0; i < 4 * KBH; ++i) scratch[lane + 64 * i] = 0.f;
   }
+  int kseq = 0;                                 // tiles this pair has walked
+  bool lost = false;                            // a hand-shake timed out (flag_wait)
   // One tile.  FULL (every tile but a run's last): 16 rows, so no per-row condition anywhere -
   // in particular the gx stores are unconditional, and the compiler's count of memory operations
   // in flight stays EXACT across the loop: the waits for the rows requested a tile ahead then do
@@ -942,18 +1019,45 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_pool_kernel(
     constexpr bool FULL = decltype(full_c)::value;
     const int64_t row0 = r0 + t * TR;
     const int cnt = FULL ? TR : cnt_of(t);
-    wave_sync_lds();
-    // ---- RAW xprev tile (gathered rows; rows >= cnt zero).  FIRST: the rows were requested
-    // before everything else of this tile, and the rare 3+-segment loop below contains loads of
-    // its own - whatever is waited for behind it is waited for with vmcnt(0)
-    store_rows<K, LDX, false, X16>(xv, cnt, nullptr, 1.f, xl, lane);
-    // ---- S tile: zero, then the winners of the tile's segments scattered into it ---------------
+    // y_prev of one raw value (rows >= cnt: 0)
+    auto ynorm = [&](float v, int k, bool ok) {
+      v = fmaf(v - pt[k], pt[K + k], pt[2 * K + k]);
+      v = (v > 0.f) ? v : v * pslope;
+      return ok ? v : 0.f;
+    };
+    if (!lost) lost = !flag_wait(flg + F_DONE + (hf ^ 1), kseq);   // the partner has read the previous tile
+    // ---- this wave's rows: RAW (rows >= cnt zero) and y_prev as bf16 planes.  FIRST: the rows
+    // were requested before everything else of this tile, and the rare 3+-segment loop below
+    // contains loads of its own - whatever is waited for behind it is waited for with vmcnt(0)
+#pragma unroll
+    for (int j = 0; j < NIT; ++j) {
+      const int q = lane + 64 * j, rl = q / CH, k = (q - rl * CH) << 2, rr = HR * hf + rl;
+      const bool ok = rr < cnt;
+      float4 w = widen<X16>(xv[j]);
+      if (!ok) w = make_float4(0.f, 0.f, 0.f, 0.f);
+      *reinterpret_cast<float4*>(xr + rr * LDX + k) = w;
+      const float yv[4] = {ynorm(w.x, k, ok), ynorm(w.y, k + 1, ok), ynorm(w.z, k + 2, ok),
+                           ynorm(w.w, k + 3, ok)};
+      bf16x4 yh, yl;
+      const int o = pl_off<K>(rr, k);
+      if constexpr (LO) {
+        split2<4>(yv, yh, yl);
+        *reinterpret_cast<bf16x4*>(yp + TR * K + o) = yl;
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) yh[i] = (__bf16)yv[i];
+      }
+      *reinterpret_cast<bf16x4*>(yp + o) = yh;
+    }
+    // ---- S planes, this wave's channels: zero, then the winners of the tile's segments ----------
     {
-      constexpr int NZ = TR * (N / 4) / 64;
 #pragma unroll
       for (int j = 0; j < NZ; ++j) {
-        const int q = lane + 64 * j, rr = q / (N / 4), n = (q - rr * (N / 4)) << 2;
-        *reinterpret_cast<float4*>(gl + rr * LDG + n) = make_float4(0.f, 0.f, 0.f, 0.f);
+        const int q = lane + 64 * j, rr = q / (NH / 8), ch = hf * (NH / 8) + (q - rr * (NH / 8));
+        const int o = pl_off<N>(rr, 8 * ch);
+        const bf16x8 z = __builtin_bit_cast(bf16x8, make_uint4(0u, 0u, 0u, 0u));
+        *reinterpret_cast<bf16x8*>(sp + o) = z;
+        if constexpr (LO) *reinterpret_cast<bf16x8*>(sp + TR * N + o) = z;
       }
       const int sA = __builtin_amdgcn_readlane(seg_l, 0);
       const int sB = __builtin_amdgcn_readlane(seg_l, cnt - 1);
@@ -968,8 +1072,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_pool_kernel(
         const int sgm = __builtin_amdgcn_readlane(seg_l, row);
         const uint64_t diff = __ballot(lane < cnt && lane > row && seg_l != sgm);
         const int e = diff ? (int)__builtin_ctzll(diff) : cnt;
-        int ap[CPL];
-        float gv[CPL];
+        int ap;
+        float gv;
         load_seg(sgm, ap, gv);
         scatter(ap, gv, (int)row0, row, e);
         row = e;
@@ -979,7 +1083,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_pool_kernel(
     // everything the NEXT tile needs from memory is requested here, before this tile's GEMMs;
     // the id registers rotate HERE, on values that have arrived (a rotation at the loop's end
     // would have to wait for the ids just requested)
-    load_rows<K, X16>(xprev, rid_n, xv, lane);
+    load_half(rid_n, xv);
     {
       const int64_t tn = t + npairs < ntiles ? t + npairs : ntiles - 1;
       load_seg(__builtin_amdgcn_readlane(seg_n, 0), apA, gvA);
@@ -988,59 +1092,52 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_pool_kernel(
     rid_l = rid_n;
     seg_l = seg_n;
     load_ids(t + 2 * npairs, rid_n, seg_n);
-    wave_sync_lds();
-    // y_prev of one raw value (rows >= cnt: 0)
-    auto ynorm = [&](float v, int k, bool ok) {
-      v = fmaf(v - pt[k], pt[K + k], pt[2 * K + k]);
-      v = (v > 0.f) ? v : v * pslope;
-      return ok ? v : 0.f;
-    };
-    // ---- gW[this half's rows] += S^T y_prev -------------------------------------------------------
+    flag_set(flg + F_STAGED + hf, kseq + 1);
+    if (!lost) lost = !flag_wait(flg + F_STAGED + (hf ^ 1), kseq + 1);
+    // ---- gW[this half's rows] += S^T y_prev: both operands through the transposed read.  Lane
+    // 4 q + p of group g supplies row 4 g + q, columns 16 b + 4 p .. + 3 and receives column 16 b + c
+    // of the rows 4 g .. 4 g + 3 --------------------------------------------------------------------
     if constexpr (!(SPT_FPOOL_SKIP & 8)) {
-      bf16x4 Xh[KB], Xl[KB];
+      const int trow = 4 * g + (c >> 2), tcol = 4 * (c & 3);
+      s16x4 Xh[KB];
+      bf16x8 Xc[LO ? KB : 1];                   // [Xh | Xl]
 #pragma unroll
       for (int kb = 0; kb < KB; ++kb) {
-        const int k = 16 * kb + c;
-        float xr4[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) xr4[r] = ynorm(xl[(4 * g + r) * LDX + k], k, 4 * g + r < cnt);
-        if constexpr (LO) {
-          split2<4>(xr4, Xh[kb], Xl[kb]);
-        } else {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) Xh[kb][r] = (__bf16)xr4[r];
-        }
+        const __bf16* p = yp + pl_off<K>(trow, 16 * kb + tcol);
+        Xh[kb] = tr_read(p);
+        if constexpr (LO)
+          Xc[kb] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(Xh[kb], tr_read(p + TR * K),
+                                                                      0, 1, 2, 3, 4, 5, 6, 7));
       }
 #pragma unroll
       for (int nb = 0; nb < NBH; ++nb) {
-        float sv[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) sv[r] = gl[(4 * g + r) * LDG + 16 * (nb0 + nb) + c];
-        bf16x4 sh, sl;
+        const __bf16* p = sp + pl_off<N>(trow, 16 * (nb0 + nb) + tcol);
+        const s16x4 sh = tr_read(p);
         if constexpr (LO) {
-          split2<4>(sv, sh, sl);
+          const s16x4 sl = tr_read(p + TR * N);
+          const bf16x8 Sc = __builtin_bit_cast(bf16x8, __builtin_shufflevector(sl, sh, 0, 1, 2, 3, 4, 5, 6, 7));   // [sl | sh]
+#pragma unroll
+          for (int kb = 0; kb < KB; ++kb) {
+            const f32x4 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Sc, Xc[kb], C3[nb][kb], 0, 0, 0);
+            C3[nb][kb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(sh, Xh[kb], acc, 0, 0, 0);
+          }
         } else {
 #pragma unroll
-          for (int r = 0; r < 4; ++r) sh[r] = (__bf16)sv[r];
-        }
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb) {
-          f32x4 acc = C3[nb][kb];
-          if constexpr (LO) {
-            acc = mfma16(sl, Xh[kb], acc);
-            acc = mfma16(sh, Xl[kb], acc);
-          }
-          C3[nb][kb] = mfma16(sh, Xh[kb], acc);
+          for (int kb = 0; kb < KB; ++kb)
+            C3[nb][kb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(sh, Xh[kb], C3[nb][kb], 0, 0, 0);
         }
       }
     }
     // ---- gy[this half's columns] = c0 + S W + y_prev M (+ statistics for the previous norm) ------
     {
       f32x4 CX[KBH];
+      float xo[4][KBH];                         // the raw values of this lane's outputs (epilogue)
 #pragma unroll
       for (int kb = 0; kb < KBH; ++kb) {
         const float z = c0l[16 * (kb0 + kb) + c];
         CX[kb] = (f32x4){z, z, z, z};
+#pragma unroll
+        for (int r = 0; r < 4; ++r) xo[r][kb] = xr[(4 * g + r) * LDX + 16 * (kb0 + kb) + c];
       }
       // (round 6: the B fragments - W^T planes, then M planes - are requested LA steps ahead of
       //  their MFMAs, as in the forward: one list of NS KBH + KS KBH (step, column block) pairs)
@@ -1068,26 +1165,10 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_pool_kernel(
         const bool first = step < NST1;
         const int sub = first ? step : step - NST1;
         const int blk = sub / KBH, kb = sub - blk * KBH;    // blk = sg (S W) or ks (y_prev M)
-        if (kb == 0) {
-          float av[8];
-          if (first) {
-            const float4 a0 = *reinterpret_cast<const float4*>(gl + c * LDG + 32 * blk + 8 * g);
-            const float4 a1 = *reinterpret_cast<const float4*>(gl + c * LDG + 32 * blk + 8 * g + 4);
-            av[0] = a0.x; av[1] = a0.y; av[2] = a0.z; av[3] = a0.w;
-            av[4] = a1.x; av[5] = a1.y; av[6] = a1.z; av[7] = a1.w;
-          } else {
-            const float4 a0 = *reinterpret_cast<const float4*>(xl + c * LDX + 32 * blk + 8 * g);
-            const float4 a1 = *reinterpret_cast<const float4*>(xl + c * LDX + 32 * blk + 8 * g + 4);
-            const float rv[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-#pragma unroll
-            for (int i = 0; i < 8; ++i) av[i] = ynorm(rv[i], 32 * blk + 8 * g + i, c < cnt);
-          }
-          if constexpr (LO) {
-            split2<8>(av, ah, alo);
-          } else {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) ah[i] = (__bf16)av[i];
-          }
+        if (kb == 0) {                          // the A fragment: row c, columns 32 blk + 8 g .. + 7
+          const __bf16* p = first ? sp + pl_off<N>(c, 32 * blk + 8 * g) : yp + pl_off<K>(c, 32 * blk + 8 * g);
+          ah = *reinterpret_cast<const bf16x8*>(p);
+          if constexpr (LO) alo = *reinterpret_cast<const bf16x8*>(p + (first ? TR * N : TR * K));
         }
         if (step + LAB < NST) ldb(step + LAB, bf[(step + LAB) % (LAB + 1)]);
         __builtin_amdgcn_sched_barrier(0);
@@ -1100,6 +1181,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_pool_kernel(
         CX[kb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, b[0], acc, 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
       }
+      flag_set(flg + F_DONE + hf, kseq + 1);    // nothing below reads the tile record
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int rr = 4 * g + r;
@@ -1110,7 +1192,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_pool_kernel(
             const int k = 16 * (kb0 + kb) + c;
             const float v = CX[kb][r];
             gx[orow * K + k] = v;
-            const float o = xl[rr * LDX + k] - pt[k];
+            const float o = xo[r][kb] - pt[k];
             float gg = v;
             if (pslope != 1.f) {
               const float y = fmaf(o, pt[K + k], pt[2 * K + k]);
@@ -1124,11 +1206,13 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_pool_kernel(
         }
       }
     }
+    ++kseq;
   };
   const int64_t nfull = (r1 - r0) / TR;         // complete tiles; at most one partial tile follows
   int64_t t = pair;
   for (; t < nfull; t += npairs) tile(std::true_type{}, t);
   if (t < ntiles) tile(std::false_type{}, t);
+  if (lost) __builtin_trap();
   }
   double* pp = pstat_partial + (size_t)pair * (2 * K + 1);
 #pragma unroll
@@ -1142,14 +1226,14 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_pool_kernel(
   }
   if (lane == 0 && hf == 0) pp[2 * K] = (pair == 0) ? (double)(r1 - r0) : 0.0;
   // gW: one table per WORKGROUP - the pairs 1 .. NW / 2 - 1 hand their tables (each wave its rows)
-  // to pair 0 through the free S-tile buffer, one pair after the other (plain stores, plain loads +
+  // to pair 0 through the free tile records, one pair after the other (plain stores, plain loads +
   // adds, fixed order); statistics: one record per pair, each wave its columns
   {
     constexpr int LDR = K + 4;                    // row stride = 4 (mod 16) floats: no bank conflicts
-    static_assert(N * LDR <= NW * TR * LDG, "the table fits the S-tile buffers");
+    static_assert(N * LDR * 4 <= NP * T_END, "the table fits the tile records");
     const int pr = wid >> 1;
     __syncthreads();                              // every wave is through its tiles
-    float* red = &g_lds[0][0];
+    float* red = reinterpret_cast<float*>(tile_lds);
 #pragma unroll 1
     for (int p = 1; p < NW / 2; ++p) {
       if (pr == p) {
