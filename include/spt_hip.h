@@ -1133,6 +1133,46 @@ int spt_cross_entropy_bwd_f32(const float* logits, const int64_t* target, const 
                               int64_t rows, int C, int64_t ignore_index, const float* gout,
                               const float* count, float* glogits, spt_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * The default semantic criterion: class weights, label-histogram targets   (train / val step)
+ * configs/model/semantic/default.yaml:7-12 (loss_type 'ce_kl', weighted_loss True) as
+ * src/models/semantic.py:397-474 builds it from CrossEntropyLoss(weight, ignore_index = C) and
+ * loss_with_target_histogram (src/utils/loss.py:25-38), with no [nnz, C] expansion and no host
+ * round trip.  logits f32 [rows, C <= 32]; weight f32 [C] or NULL (ones); mode:
+ *   0 index:     target int64 [rows]; rows with target == ignore_index do not count
+ *                loss = sum w[t] (lse - z[t]) / sum w[t]
+ *   1 dominant:  target int64 [rows, ncols] label counts, ncols in {C, C + 1} (column C = void);
+ *                t = first index of the row maximum over all ncols columns, t == C is ignored;
+ *                the formula of mode 0
+ *   2 histogram: loss = sum_r sum_{c < C} h[r, c] w[c] (lse_r - z[r, c]) / sum_r sum_{c < ncols} h[r, c]
+ *                (the void column counts in the denominator only; class weights do not enter it)
+ *   fwd: loss[1] f32, den[1] f64 (the denominator; exact for counts below 2^53);
+ *        ws: spt_cross_entropy_workspace_bytes(rows).  Deterministic (f64 partial sums, fixed order).
+ *        A label outside [0, C) other than ignore_index, or a negative count, makes the loss NaN;
+ *        den == 0 (every row ignored / empty) gives NaN like the reference's 0 / 0.
+ *        confmat (modes 1 / 2; may be NULL): int64 [C, C], confmat[t, argmax z[r]] += h[r, t] for
+ *        t < C (first maximum), ADDED to what the caller's buffer holds (integer atomics: exact in
+ *        any order).
+ *   bwd: glogits[r, c] = gout[0] (S_r softmax(z[r])[c] - hw[r, c]) / den[0], with hw = h w and
+ *        S_r = sum_{c < C} hw[r, c] (mode 2), hw = w[t] onehot(t) and S_r = w[t] (modes 0 / 1; 0
+ *        for ignored rows).  gout / den are device scalars.  The softmax is recomputed from the
+ *        logits and the difference formed in f64. */
+int spt_hist_loss_fwd_f32(const float* logits, const int64_t* target, int64_t rows, int C, int ncols,
+                          int mode, int64_t ignore_index, const float* weight, float* loss,
+                          double* den, int64_t* confmat, void* ws, size_t ws_bytes,
+                          spt_stream_t stream);
+int spt_hist_loss_bwd_f32(const float* logits, const int64_t* target, int64_t rows, int C, int ncols,
+                          int mode, int64_t ignore_index, const float* weight, const float* gout,
+                          const double* den, float* glogits, spt_stream_t stream);
+/* Confusion matrix from segment-level predictions and label histograms, without flattening them
+ * to points (ConfusionMatrix.update, src/metrics/semantic.py:66-107): confmat[t, pred[r]] +=
+ * h[r, t] for t < C <= 32 (target int64 [rows, ncols >= C]; columns past C are void), or, with
+ * ncols == 0, confmat[target[r], pred[r]] += 1 for int64 labels in [0, C) (any other label is
+ * void).  int64 [C, C], ADDED to what the buffer holds; rows whose prediction is not in [0, C) are
+ * dropped. */
+int spt_confusion_matrix_i64(const int64_t* pred, const int64_t* target, int64_t rows, int C,
+                             int ncols, int64_t* confmat, spt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

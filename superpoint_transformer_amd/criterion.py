@@ -1,0 +1,85 @@
+"""The semantic criterion of the reference's default configuration, on the histogram-loss kernels.
+
+``configs/model/semantic/default.yaml:7-12`` trains with ``loss_type: 'ce_kl'``,
+``weighted_loss: True`` and ``multi_stage_loss_lambdas: [1, 50]`` on the per-superpoint label
+histograms ``nag[i].y`` (int64 [N_i, C + 1], last column void).  ``SemanticCriterion`` combines
+``ops.histogram_loss`` per level exactly as ``src/models/semantic.py:397-474`` combines
+``CrossEntropyLoss(weight, ignore_index=C)`` and ``loss_with_target_histogram``; on CUDA tensors
+nothing in it waits on the host, so a step with it can be captured into a graph.
+
+``'wce'`` and ``'wce_kl'`` are refused.  The reference builds their target with
+``y_hist_dominant[:, y_dominant] = y.sum(dim=1)`` (``semantic.py:405-406``, ``:440-441``), an
+advanced-index assignment that writes every row's total into every row and whose winner among
+duplicate indices is unspecified: there is no well-defined behaviour to reproduce.
+"""
+import torch
+
+from . import ops
+
+LOSS_TYPES = ("ce", "kl", "ce_kl")
+_REFUSED = ("wce", "wce_kl")
+
+
+class SemanticCriterion(torch.nn.Module):
+    """``criterion(logits, y_hist)``: [rows, C] logits against an int64 [rows, C or C + 1] label
+    histogram (single stage: ``'ce'`` or ``'kl'``), or lists of both, one per level, finest first
+    (multi stage: ``'ce'``, ``'kl'`` or ``'ce_kl'``, weighted by ``lambdas``):
+
+    - ``'ce'``: class-weighted CE on the dominant label of each histogram, ``sum_i lambda_i CE_i``;
+    - ``'kl'``: class-weighted CE against the whole histogram, ``sum_i lambda_i KL_i``;
+    - ``'ce_kl'``: ``CE_0 + sum_{i >= 1} lambda_i KL_i`` (the first level carries no lambda,
+      ``semantic.py:425-427``).
+
+    ``weight``: float [C] class weights or None; a buffer, assignable after construction as the
+    reference's ``on_fit_start`` does (``semantic.py:337-350``).  ``confmat``: optional int64
+    [C, C] buffer (``metrics.ConfusionMatrix.confmat``) that receives, from the same pass, the
+    confusion matrix of the first level's ``argmax logits`` against its histogram."""
+
+    def __init__(self, num_classes, loss_type="ce_kl", lambdas=(1, 50), weight=None):
+        super().__init__()
+        if loss_type in _REFUSED:
+            raise ValueError(
+                f"loss_type {loss_type!r} is not supported: the reference builds its target with "
+                "`y_hist_dominant[:, y_dominant] = y.sum(dim=1)`, an advanced-index assignment with "
+                "duplicate indices whose result is unspecified - there is nothing well-defined to "
+                "reproduce")
+        if loss_type not in LOSS_TYPES:
+            raise ValueError(f"unknown loss_type {loss_type!r}: one of {LOSS_TYPES}")
+        self.num_classes = int(num_classes)
+        self.loss_type = loss_type
+        self.lambdas = [float(l) for l in lambdas]
+        self.register_buffer("weight", None)
+        if weight is not None:
+            self.weight = torch.as_tensor(weight, dtype=torch.float32)
+
+    def extra_repr(self):
+        return f"num_classes={self.num_classes}, loss_type={self.loss_type!r}, lambdas={self.lambdas}"
+
+    def _level(self, kind, logits, y_hist, confmat=None):
+        if logits.dim() != 2 or logits.shape[1] != self.num_classes:
+            raise ValueError(f"logits must be [rows, {self.num_classes}], got {tuple(logits.shape)}")
+        w = self.weight
+        if w is not None and w.device != logits.device:
+            w = w.to(logits.device)
+        return ops.histogram_loss(logits, y_hist, weight=w, confmat=confmat,
+                                  mode="dominant" if kind == "ce" else "histogram")
+
+    def forward(self, logits, y_hist, confmat=None):
+        multi = isinstance(logits, (list, tuple))
+        if multi != isinstance(y_hist, (list, tuple)):
+            raise ValueError("pass logits and histograms both as tensors or both as lists")
+        if not multi:
+            if self.loss_type not in ("ce", "kl"):
+                raise ValueError(f"Unknown single-stage loss {self.loss_type!r}")
+            return self._level(self.loss_type, logits, y_hist, confmat)
+        if not len(logits) == len(y_hist) == len(self.lambdas):
+            raise ValueError(f"{len(logits)} logits, {len(y_hist)} histograms, "
+                             f"{len(self.lambdas)} lambdas: one of each per level")
+        loss = 0
+        for i, (lamb, a, b) in enumerate(zip(self.lambdas, logits, y_hist)):
+            cm = confmat if i == 0 else None
+            if self.loss_type == "ce_kl" and i == 0:
+                loss = loss + self._level("ce", a, b, cm)
+            else:
+                loss = loss + lamb * self._level("ce" if self.loss_type == "ce" else "kl", a, b, cm)
+        return loss

@@ -183,9 +183,13 @@ class _NagView:
 class SPTTrainStep:
     name = "SPT-64 (spt-2, S3DIS cfg) fwd + CE loss + bwd + AdamW, incl. per-batch CSR builds"
 
-    def __init__(self, nag, dev, world=1, seed=0, model="spt64", kernel_timers=False):
+    def __init__(self, nag, dev, world=1, seed=0, model="spt64", kernel_timers=False,
+                 criterion=None, targets=None):
         """``kernel_timers``: HIP-event timers around the north-star kernel and the ops leading the
-        step (what ``roofline()`` reports) - a measurement aid, off unless asked for (bench.py)."""
+        step (what ``roofline()`` reports) - a measurement aid, off unless asked for (bench.py).
+        ``criterion`` + ``targets``: a ``criterion.SemanticCriterion`` and the label histograms
+        ``nag[i].y`` of the output levels (int64 [N_i, C or C + 1], finest first): the step then
+        trains with the reference's default loss instead of plain CE on the random labels."""
         self.nag, self.dev, self.world = _NagView(nag), dev, world
         self.n = nag.num_points
         self.net_name = model
@@ -209,6 +213,10 @@ class SPTTrainStep:
                        for i in (1, 2)]
         self.lambdas = [1.0, 50.0]               # configs/model/semantic/default.yaml:12
         self.loss_fn = ops.cross_entropy          # CrossEntropyLoss(), mean reduction, on csrc/loss.hip
+        if (criterion is None) != (targets is None):
+            raise ValueError("pass a criterion together with its per-level target histograms")
+        self.criterion = criterion.to(dev) if criterion is not None else None
+        self.targets = [t.to(dev) for t in targets] if targets is not None else None
         n0, c = self.n[0], 128
         self.tname = f"segcsr_reduce_fwd:3:{n0}x{c}"
         self.k_timers = None
@@ -244,12 +252,16 @@ class SPTTrainStep:
 
     _timed_steps = 0
     graph = None                      # a captured step (capture()): replayed by step()
+    criterion = targets = None        # the default loss: plain CE on `labels`
 
     def _fwd_bwd(self):
         """Forward + loss + backward of the batch: every CSR view, run table and gradient rebuilt."""
         self._forget_csr()
         logits = self.model(self.nag)
-        loss = sum(l * self.loss_fn(lg, y) for l, lg, y in zip(self.lambdas, logits, self.labels))
+        if self.criterion is not None:
+            loss = self.criterion(logits, self.targets)
+        else:
+            loss = sum(l * self.loss_fn(lg, y) for l, lg, y in zip(self.lambdas, logits, self.labels))
         self.bucket.zero()
         loss.backward()
         return loss

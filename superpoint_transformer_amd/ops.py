@@ -1,7 +1,10 @@
 """Functional, differentiable front-ends of the HIP segment kernels.
 
 Every function here launches a kernel of libspt_hip.so on torch's current
-stream; there is no eager-PyTorch path.
+stream; there is no eager-PyTorch path.  The one exception is the criterion
+(``histogram_loss``, ``cross_entropy(weight=...)``, ``histogram_confusion_matrix``):
+CPU tensors and heads wider than 32 classes take a torch composition of the
+same closed forms, so that criterion and metric modules also run off the device.
 """
 import ctypes
 import os
@@ -1278,13 +1281,184 @@ class _CrossEntropy(torch.autograd.Function):
         return glog.to(dtype), None, None
 
 
-def cross_entropy(logits, target, ignore_index=-100):
-    """``torch.nn.functional.cross_entropy(logits, target, ignore_index=...)`` (mean reduction, no
-    class weights) for [rows, C <= 32] logits on the HIP kernels; anything else goes to torch."""
+def cross_entropy(logits, target, ignore_index=-100, weight=None):
+    """``torch.nn.functional.cross_entropy(logits, target, weight=..., ignore_index=...)`` (mean
+    reduction) for [rows, C <= 32] logits on the HIP kernels; anything else goes to torch.  With
+    class weights (``weighted_loss: True``) the mean is over ``sum w[target]`` (index mode of the
+    histogram-loss kernels below)."""
+    if weight is not None:
+        return _hist_loss(logits, target, weight, HL_INDEX, ignore_index, None)
     if (logits.is_cuda and logits.dim() == 2 and 1 <= logits.shape[1] <= 32
             and logits.shape[0] >= 1 and target.dim() == 1):
         return _CrossEntropy.apply(logits, target, ignore_index)
     return torch.nn.functional.cross_entropy(logits, target, ignore_index=ignore_index)
+
+
+# ---------------------------------------------------------------------------
+# Class-weighted CE on label histograms + histogram confusion matrix (csrc/loss.hip): the
+# reference's default criterion (loss_type 'ce_kl', weighted_loss True) and its metric
+# ---------------------------------------------------------------------------
+HL_INDEX, HL_DOMINANT, HL_HISTOGRAM = 0, 1, 2
+_HL_MODES = {"index": HL_INDEX, "dominant": HL_DOMINANT, "histogram": HL_HISTOGRAM}
+
+
+def _check_hist(logits, target, mode):
+    if logits.dim() != 2 or not logits.is_floating_point():
+        raise ValueError(f"logits must be a floating [rows, C] tensor, got {tuple(logits.shape)}")
+    c = logits.shape[1]
+    if target.is_floating_point() or target.shape[0] != logits.shape[0]:
+        raise ValueError("the target must be an integer tensor with one row per logits row")
+    if mode == HL_INDEX:
+        if target.dim() != 1:
+            raise ValueError(f"index targets are [rows], got {tuple(target.shape)}")
+    elif target.dim() != 2 or target.shape[1] not in (c, c + 1):
+        raise ValueError(f"a label histogram for {c} classes has {c} or {c + 1} (void) columns, "
+                         f"got {tuple(target.shape)}")
+
+
+def _hist_loss_torch(logits, target, weight, mode, ignore_index):
+    """The closed forms of the kernels as a torch composition (CPU tensors, C > 32): fixed output
+    sizes only - no ``where(mask)``, no ``repeat_interleave`` - so nothing waits on the host."""
+    z = logits
+    c = z.shape[1]
+    w = torch.ones(c, dtype=z.dtype, device=z.device) if weight is None else weight.to(z.dtype)
+    lse = torch.logsumexp(z, dim=1)
+    nan = torch.full((), float("nan"), dtype=z.dtype, device=z.device)
+    if mode == HL_HISTOGRAM:
+        hw = target[:, :c].to(z.dtype) * w
+        num = torch.where(hw != 0, hw * (lse[:, None] - z), torch.zeros_like(z)).sum()
+        den = target.sum().to(z.dtype)
+        bad = (target < 0).any()
+    else:
+        if mode == HL_DOMINANT:
+            t, ignore_index, bad = target.argmax(dim=1), c, (target < 0).any()
+        else:
+            t = target
+            bad = ((t != ignore_index) & ((t < 0) | (t >= c))).any()
+        tc = t.clamp(0, c - 1)
+        wt = w[tc] * ((t != ignore_index) & (t >= 0) & (t < c)).to(z.dtype)
+        num = (wt * (lse - z.gather(1, tc[:, None])[:, 0])).sum()
+        den = wt.sum()
+    return torch.where(bad, nan, num) / den
+
+
+class _HistLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, weight, mode, ignore_index, confmat):
+        _lib.require_cuda(logits, target, weight, confmat)
+        lg = _f32c(logits)
+        tg = target.long().contiguous()
+        wt = _f32c(weight)
+        rows, c = lg.shape
+        ncols = tg.shape[1] if tg.dim() == 2 else 0
+        dev = lg.device
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        den = torch.empty(1, dtype=torch.float64, device=dev)
+        ws = _workspace(_lib.lib.spt_cross_entropy_workspace_bytes(rows), dev)
+        with torch.cuda.device(dev):
+            st = _lib.lib.spt_hist_loss_fwd_f32(
+                _lib.ptr(lg), _lib.ptr(tg), rows, c, ncols, mode, int(ignore_index), _lib.ptr(wt),
+                _lib.ptr(loss), _lib.ptr(den), _lib.ptr(confmat), _lib.ptr(ws), ws.numel(),
+                _lib.stream_ptr(dev))
+        _lib.check(st, "spt_hist_loss_fwd_f32")
+        ctx.save_for_backward(lg, tg, wt, den)
+        ctx.meta = (mode, int(ignore_index), logits.dtype)
+        return loss[0].to(logits.dtype)
+
+    @staticmethod
+    def backward(ctx, gout):
+        lg, tg, wt, den = ctx.saved_tensors
+        mode, ignore_index, dtype = ctx.meta
+        rows, c = lg.shape
+        ncols = tg.shape[1] if tg.dim() == 2 else 0
+        dev = lg.device
+        g = gout.detach().float().reshape(1).contiguous()
+        glog = torch.empty_like(lg)
+        with torch.cuda.device(dev):
+            st = _lib.lib.spt_hist_loss_bwd_f32(
+                _lib.ptr(lg), _lib.ptr(tg), rows, c, ncols, mode, ignore_index, _lib.ptr(wt),
+                _lib.ptr(g), _lib.ptr(den), _lib.ptr(glog), _lib.stream_ptr(dev))
+        _lib.check(st, "spt_hist_loss_bwd_f32")
+        return glog.to(dtype), None, None, None, None, None
+
+
+def _hist_loss(logits, target, weight, mode, ignore_index, confmat):
+    _check_hist(logits, target, mode)
+    c = logits.shape[1]
+    if weight is not None and tuple(weight.shape) != (c,):
+        raise ValueError(f"class weights must be [{c}], got {tuple(weight.shape)}")
+    if confmat is not None and (mode == HL_INDEX or confmat.dtype != torch.int64
+                                or tuple(confmat.shape) != (c, c) or not confmat.is_contiguous()):
+        raise ValueError(f"the fused confusion matrix is a contiguous int64 [{c}, {c}] buffer "
+                         "and needs histogram targets")
+    if logits.is_cuda and c <= 32 and logits.shape[0] >= 1:
+        return _HistLoss.apply(logits, target, weight, mode, ignore_index, confmat)
+    if confmat is not None:
+        histogram_confusion_matrix(logits.detach(), target, c, out=confmat)
+    return _hist_loss_torch(logits, target, weight, mode, ignore_index)
+
+
+def histogram_loss(logits, y_hist, weight=None, mode="histogram", confmat=None):
+    """Class-weighted cross-entropy of [rows, C] logits against int64 label histograms
+    ``y_hist`` [rows, C or C + 1] (last column void when C + 1), differentiable in ``logits``:
+
+    ``mode="histogram"``: ``loss_with_target_histogram(CrossEntropyLoss(weight, ignore_index=C),
+    logits, y_hist)`` of the reference (src/utils/loss.py:25-38) in closed form,
+    ``sum h[r, c] w[c] (lse_r - z[r, c]) / sum h`` (the void column counts in the denominator only);
+    ``mode="dominant"``: ``CrossEntropyLoss(weight, ignore_index=C)(logits, y_hist.argmax(1))``.
+
+    ``confmat``: optional int64 [C, C] buffer; the confusion matrix of ``argmax logits`` against
+    the histograms is ADDED to it by the same pass (a validation step's loss and metric together).
+    CUDA tensors with C <= 32 run on the HIP kernels (no host synchronisation: the call can be
+    captured into a graph); CPU tensors and wider heads take a sync-free torch composition."""
+    if mode not in ("histogram", "dominant"):
+        raise ValueError(f"mode must be 'histogram' or 'dominant', got {mode!r}")
+    return _hist_loss(logits, y_hist, weight, _HL_MODES[mode], -100, confmat)
+
+
+def histogram_confusion_matrix(pred, target, num_classes, out=None):
+    """Confusion matrix [num_classes, num_classes] (int64, ``[true, predicted]``) of segment-level
+    predictions against label histograms, as the reference's ``ConfusionMatrix.update``
+    (src/metrics/semantic.py:66-107) accumulates it - in exact integers, where the reference sums
+    in float32: ``out[t, pred[r]] += target[r, t]`` for ``t < num_classes`` (further columns are
+    void).  ``pred``: int labels [rows] or [rows, num_classes] logits / probabilities (first
+    maximum).  A 1-D (or [rows, 1]) ``target`` holds labels: those outside [0, num_classes) are
+    void.  ``out``: an int64 buffer to ACCUMULATE into (returned); a fresh zero matrix if None."""
+    c = int(num_classes)
+    if pred.dim() == 2:
+        pred = pred.argmax(dim=1)
+    pred = pred.long()
+    if target.is_floating_point() or target.dim() not in (1, 2) or target.shape[0] != pred.shape[0]:
+        raise ValueError("the target must be an integer [rows] or [rows, ncols] tensor matching pred")
+    if target.dim() == 2 and target.shape[1] == 1 and c > 1:
+        target = target[:, 0]
+    if target.dim() == 2 and target.shape[1] < c:
+        raise ValueError(f"a label histogram for {c} classes has at least {c} columns, "
+                         f"got {tuple(target.shape)}")
+    if out is None:
+        out = torch.zeros(c, c, dtype=torch.int64, device=pred.device)
+    elif out.dtype != torch.int64 or tuple(out.shape) != (c, c) or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous int64 [{c}, {c}] tensor")
+    rows = pred.shape[0]
+    if rows == 0:
+        return out
+    if pred.is_cuda and c <= 32:
+        _lib.require_cuda(target, out)
+        pr, tg = pred.contiguous(), target.long().contiguous()
+        with torch.cuda.device(pred.device):
+            st = _lib.lib.spt_confusion_matrix_i64(
+                _lib.ptr(pr), _lib.ptr(tg), rows, c, tg.shape[1] if tg.dim() == 2 else 0,
+                _lib.ptr(out), _lib.stream_ptr(pred.device))
+        _lib.check(st, "spt_confusion_matrix_i64")
+        return out
+    ok = (pred >= 0) & (pred < c)
+    pc = pred.clamp(0, c - 1)
+    if target.dim() == 2:
+        out.index_add_(1, pc, (target[:, :c].long() * ok[:, None]).t().contiguous())
+    else:
+        ok = ok & (target >= 0) & (target < c)
+        out.view(-1).index_add_(0, target.long().clamp(0, c - 1) * c + pc, ok.long())
+    return out
 
 
 # ---------------------------------------------------------------------------
