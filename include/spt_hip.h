@@ -678,6 +678,59 @@ int spt_cluster_pair_anchors_f32(const float* points, const int32_t* perm, const
                                  int64_t* anchors, float* d_nn, spt_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Input graph of the partition, from the kNN table
+ * AdjacencyGraph(k, w)._process (src/transforms/graph.py:67-96), Data.connect_isolated
+ * (src/data/data.py:481-561; isolated_nodes, src/utils/graph.py:44-53), Data.to_trimmed
+ * (data.py:563-586; src/utils/graph.py:466-502) and the forward star of the sorted edges
+ * (src/transforms/partition.py:190-196), without the edge list, its unique() and the
+ * coalesce sort: the mirror of entry i -> j is one of the first k entries of row j.
+ *
+ * neighbors [n, ld] int64 (any negative entry = missing), distances [n, ld] f32 (nullable
+ * when w <= 0); the first k <= min(ld, 64) columns are read in place.  n < 2^31.
+ *
+ * spt_adjacency_stats: linked [n] u8 = 1 for every source and every target of a directed
+ *   edge (graph.py:44-53 negated); stats: 4 device doubles = number of valid entries, sum of
+ *   their distances (f64; mean of graph.py:92), number of isolated nodes, flag word (1: a row
+ *   names a node twice among its first k entries - the entries below do not apply, 2: an
+ *   entry >= n).
+ * spt_adjacency_regression: sums: 4 device doubles = sum d, sum d^2, sum wgt, sum d wgt over
+ *   the valid entries, d = |pos_i - pos_j|, wgt = 1 / (w + dist / mean) or 1 (w <= 0): with
+ *   the entry count, the normal equations of the lstsq of data.py:535-545.  Workspace: the
+ *   one of spt_adjacency_stats.
+ * spt_adjacency_count: the isolated nodes' new edges (data.py:519-524) are extra rows:
+ *   node iso_index[q] (ascending), entries iso_neighbors [num_isolated, k_isolated].  An entry
+ *   i -> j, j != i, survives iff i < j or node j does not list i.  keep [n + num_isolated]:
+ *   one bit per column; row_start [n + 1] u32: first output slot of every smaller end point,
+ *   row_start[n] = number of edges.
+ * spt_adjacency_fill: edge_index [2, num_edges] int64 sorted by (i, j), i < j (coalesce's
+ *   order); edge_attr [num_edges] f32 (nullable: no weights) - both directions of a pair
+ *   merged with reduce (0 mean, 1 add, 2 min, 3 max), the extra rows' weights given in
+ *   iso_weights [num_isolated, k_isolated] (data.py:556); source_csr [n + 1] int64.
+ *   Bitwise reproducible.
+ * ---------------------------------------------------------------------- */
+size_t spt_adjacency_stats_workspace_bytes(int64_t num_nodes);
+int spt_adjacency_stats(const int64_t* neighbors, const float* distances, int64_t num_nodes,
+                        int64_t ld, int k, uint8_t* linked, double* stats, void* ws,
+                        size_t ws_bytes, spt_stream_t stream);
+int spt_adjacency_regression(const int64_t* neighbors, const float* distances, const float* pos,
+                             int64_t num_nodes, int64_t ld, int k, float w, float mean,
+                             double* sums, void* ws, size_t ws_bytes, spt_stream_t stream);
+size_t spt_adjacency_count_workspace_bytes(int64_t num_nodes);
+int spt_adjacency_count(const int64_t* neighbors, int64_t num_nodes, int64_t ld, int k,
+                        const uint8_t* linked, const int64_t* iso_index,
+                        const int64_t* iso_neighbors, int64_t num_isolated, int k_isolated,
+                        uint64_t* keep, uint32_t* row_start, void* ws, size_t ws_bytes,
+                        spt_stream_t stream);
+size_t spt_adjacency_fill_workspace_bytes(int64_t num_nodes, int64_t num_edges);
+int spt_adjacency_fill(const int64_t* neighbors, const float* distances, int64_t num_nodes,
+                       int64_t ld, int k, float w, float mean, const uint8_t* linked,
+                       const int64_t* iso_index, const int64_t* iso_neighbors,
+                       const float* iso_weights, int64_t num_isolated, int k_isolated, int reduce,
+                       const uint64_t* keep, const uint32_t* row_start, int64_t num_edges,
+                       int64_t* edge_index, float* edge_attr, int64_t* source_csr, void* ws,
+                       size_t ws_bytes, spt_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * NAG selection / re-indexing                                             (f3)
  * The integer work of NAG.select (src/data/nag.py:306-399), Data.select
  * (src/data/data.py:286-470) and Cluster.select (src/data/cluster.py:79-140).  All ids

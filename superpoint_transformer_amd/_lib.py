@@ -220,6 +220,14 @@ SIGNATURES = {
     "spt_radius_ball_workspace_bytes": (_sz, [_i64]),
     "spt_radius_ball_f32": (_int, [_p, _i64, _p, _f32, _int, _p, _i64, _p, _p, _p, _sz, _p]),
     "spt_cluster_pair_anchors_f32": (_int, [_p, _p, _p, _p, _p, _i64, _i64, _int, _int, _p, _p, _p]),
+    "spt_adjacency_stats_workspace_bytes": (_sz, [_i64]),
+    "spt_adjacency_stats": (_int, [_p, _p, _i64, _i64, _int, _p, _p, _p, _sz, _p]),
+    "spt_adjacency_regression": (_int, [_p, _p, _p, _i64, _i64, _int, _f32, _f32, _p, _p, _sz, _p]),
+    "spt_adjacency_count_workspace_bytes": (_sz, [_i64]),
+    "spt_adjacency_count": (_int, [_p, _i64, _i64, _int, _p, _p, _p, _i64, _int, _p, _p, _p, _sz, _p]),
+    "spt_adjacency_fill_workspace_bytes": (_sz, [_i64, _i64]),
+    "spt_adjacency_fill": (_int, [_p, _p, _i64, _i64, _int, _f32, _f32, _p, _p, _p, _p, _i64, _int, _int,
+                                  _p, _p, _i64, _p, _p, _p, _p, _sz, _p]),
 }
 
 

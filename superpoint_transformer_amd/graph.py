@@ -14,7 +14,8 @@ from . import _lib
 from .csr import csr_of
 from .ops import segment_reduce
 
-__all__ = ["to_trimmed", "edge_wise_points", "base_vectors_3d", "subedges"]
+__all__ = ["to_trimmed", "edge_wise_points", "base_vectors_3d", "subedges",
+           "partition_adjacency", "PartitionGraph"]
 
 
 def to_trimmed(edge_index):
@@ -183,3 +184,275 @@ def subedges(points, index, edge_index, ratio=0.2, k_min=20, cycles=3, pca_on_cp
     S_idx, S_uid = sort_along(S_pts, S_idx, S_uid, s_v)
     T_idx, T_uid = sort_along(T_pts, T_idx, T_uid, t_v)
     return edge_index, torch.vstack((S_idx, T_idx)), S_uid
+
+
+# ---------------------------------------------------------------------------
+# Input graph of the partition: kNN table -> trimmed, weighted forward star
+# ---------------------------------------------------------------------------
+_REDUCE_CODES = {"mean": 0, "add": 1, "sum": 1, "min": 2, "max": 3}
+
+
+class PartitionGraph:
+    """What ``partition_adjacency`` returns: ``edge_index`` [2, E] int64 (i < j, sorted by
+    (i, j)), ``edge_attr`` [E] f32 or None, ``source_csr`` [N + 1] int64 (row pointers over
+    ``edge_index[0]``) and ``num_isolated``.  ``target`` is ``edge_index[1]``; the forward
+    star's ``reindex`` is the identity since the edges are sorted."""
+    __slots__ = ("edge_index", "edge_attr", "source_csr", "num_isolated")
+
+    def __init__(self, edge_index, edge_attr, source_csr, num_isolated):
+        self.edge_index, self.edge_attr = edge_index, edge_attr
+        self.source_csr, self.num_isolated = source_csr, int(num_isolated)
+
+    @property
+    def target(self):
+        return self.edge_index[1]
+
+
+def _regression_line(n, sd, sdd, sw, sdw):
+    """Least-squares ``(a, b)`` of ``a d + b = w`` from the five sums (data.py:535-545).  A
+    rank-deficient system (every distance equal) gets lstsq's minimum-norm solution."""
+    det = n * sdd - sd * sd
+    if n > 0 and det > 1e-12 * max(n * sdd, 1e-300):
+        a = (n * sdw - sd * sw) / det
+        return a, (sw - a * sd) / n
+    if n <= 0:
+        return 0.0, 0.0
+    d0, w0 = sd / n, sw / n                      # rows all equal [d0, 1]: x = w0 [d0, 1] / (d0^2 + 1)
+    return w0 * d0 / (d0 * d0 + 1.0), w0 / (d0 * d0 + 1.0)
+
+
+def _knn_isolated_torch(pos, query, k, r_max, batch_search, batch_query):
+    """``knn_2`` by exhaustive search, for CPU tensors: the k nearest within ``r_max`` (squared
+    distance < r_max^2 in f32, ties by index, -1 padding; squared distances returned)."""
+    s, q = pos.float(), query.float()
+    if batch_search is not None:
+        z = torch.cat((s[:, 2], q[:, 2]))
+        zoff = z.max() - z.min() + r_max + 1
+        s, q = s.clone(), q.clone()
+        s[:, 2] += batch_search.to(s.dtype) * zoff
+        q[:, 2] += batch_query.to(q.dtype) * zoff
+    diff = q[:, None, :] - s[None, :, :]
+    d2 = (diff[..., 0] * diff[..., 0] + diff[..., 1] * diff[..., 1]) + diff[..., 2] * diff[..., 2]
+    r2 = torch.tensor(float(r_max), dtype=torch.float32) ** 2
+    d2 = torch.where(d2 < r2, d2, torch.full_like(d2, float("inf")))
+    kk = min(k, s.shape[0])
+    dsel, order = torch.sort(d2, dim=1, stable=True)
+    dsel, order = dsel[:, :kk], order[:, :kk]
+    nb = torch.full((q.shape[0], k), -1, dtype=torch.long, device=pos.device)
+    dd = torch.full((q.shape[0], k), -1.0, dtype=torch.float32, device=pos.device)
+    good = torch.isfinite(dsel)
+    nb[:, :kk] = torch.where(good, order, torch.full_like(order, -1))
+    dd[:, :kk] = torch.where(good, dsel, torch.full_like(dsel, -1.0))
+    return nb, dd
+
+
+def _coalesce_torch(edge_index, edge_attr, reduce):
+    """``coalesce`` in plain torch, for CPU tensors (the device route uses the shims')."""
+    n = int(edge_index.max()) + 1 if edge_index.numel() else 1
+    uniq, inv = torch.unique(edge_index[0] * n + edge_index[1], sorted=True, return_inverse=True)
+    ei = torch.stack([uniq // n, uniq % n])
+    if edge_attr is None:
+        return ei, None
+    red = {"mean": "mean", "add": "sum", "sum": "sum", "min": "amin", "max": "amax"}[reduce]
+    out = torch.zeros(uniq.numel(), dtype=edge_attr.dtype, device=edge_attr.device)
+    return ei, out.scatter_reduce(0, inv, edge_attr, red, include_self=False)
+
+
+def _isolated_edges(pos, is_out, k_isolated, batch):
+    """New edges of the isolated nodes (data.py:506-524): ``(neighbors, distances)`` of the
+    ``k_isolated`` nearest other nodes, column 0 of a ``k_isolated + 1`` search dropped."""
+    r_max = float((pos.max(dim=0).values - pos.min(dim=0).values).norm())
+    bq = batch[is_out] if batch is not None else None
+    if not r_max > 0:                                   # one node, or all at one place: d < r_max never holds
+        shape = (is_out.numel(), k_isolated)
+        return (torch.full(shape, -1, dtype=torch.long, device=pos.device),
+                torch.full(shape, -1.0, dtype=torch.float32, device=pos.device))
+    if pos.is_cuda:
+        from .neighbors import knn_2
+        nb, d = knn_2(pos, pos[is_out], k_isolated + 1, r_max=r_max, batch_search=batch,
+                      batch_query=bq)
+    else:
+        nb, d = _knn_isolated_torch(pos, pos[is_out], k_isolated + 1, r_max, batch, bq)
+    return nb.view(-1, k_isolated + 1)[:, 1:].contiguous(), d.view(-1, k_isolated + 1)[:, 1:].contiguous()
+
+
+def _partition_adjacency_torch(neighbor_index, neighbor_distance, k, w, pos, k_isolated, reduce,
+                               batch):
+    """The reference's composition step by step in torch (graph.py:77-94, data.py:490-561,
+    utils/graph.py:466-502): the route of CPU tensors and of tables whose rows repeat a
+    neighbour.  Duplicates are merged by a sort (``coalesce``), the regression line comes from
+    the same five f64 sums as on the device."""
+    N = neighbor_index.shape[0]
+    dev = neighbor_index.device
+    source = torch.arange(N, device=dev).repeat_interleave(k)
+    target = neighbor_index[:, :k].flatten()
+    mask = target >= 0
+    source, target = source[mask], target[mask]
+    if w > 0:
+        distances = neighbor_distance[:, :k].flatten()[mask].float()
+        mean = (distances.double().sum() / max(distances.numel(), 1)).float()
+        edge_attr = 1 / (w + distances / mean)
+    else:
+        edge_attr = torch.ones_like(source, dtype=torch.float)
+    if source.numel() == 0:
+        edge_attr = None                                              # data.py:492-494
+    linked = torch.zeros(N, dtype=torch.bool, device=dev)
+    linked[source] = True
+    linked[target] = True
+    is_out = torch.where(~linked)[0]
+    if k_isolated > 0 and is_out.numel() > 0:
+        if pos is None:
+            raise ValueError("isolated nodes need pos to be connected")
+        nb, dist = _isolated_edges(pos, is_out, k_isolated, batch)
+        new_s, new_t, dist = is_out.repeat_interleave(k_isolated), nb.flatten(), dist.flatten()
+        found = new_t >= 0
+        if edge_attr is not None:
+            d = (pos[source] - pos[target]).float().norm(dim=1).double()
+            wd = edge_attr.double()
+            a, b = _regression_line(float(d.numel()), float(d.sum()), float((d * d).sum()),
+                                    float(wd.sum()), float((d * wd).sum()))
+            new_w = dist * torch.tensor(a, dtype=torch.float32, device=dev) \
+                + torch.tensor(b, dtype=torch.float32, device=dev)
+            edge_attr = torch.cat((edge_attr, new_w[found]))
+        source, target = torch.cat((source, new_s[found])), torch.cat((target, new_t[found]))
+    lo, hi = torch.minimum(source, target), torch.maximum(source, target)
+    edge_index = torch.stack((lo, hi))
+    if dev.type == "cuda" and edge_index.numel():
+        from .shims.pyg_shim import coalesce
+        edge_index, edge_attr = coalesce(edge_index, edge_attr, reduce=reduce)
+    else:
+        edge_index, edge_attr = _coalesce_torch(edge_index, edge_attr, reduce)
+    keep = edge_index[0] != edge_index[1]
+    edge_index = edge_index[:, keep]
+    edge_attr = None if edge_attr is None else edge_attr[keep]
+    csr = torch.zeros(N + 1, dtype=torch.long, device=dev)
+    csr[1:] = torch.cumsum(torch.bincount(edge_index[0], minlength=N), 0)
+    return PartitionGraph(edge_index, edge_attr, csr, is_out.numel())
+
+
+def partition_adjacency(neighbor_index, neighbor_distance, k, w=-1, pos=None, k_isolated=1,
+                        reduce="mean", batch=None):
+    """The partition's input graph from the kNN table: ``AdjacencyGraph(k, w)`` ->
+    ``ConnectIsolated(k_isolated)`` -> ``Data.to_trimmed(reduce)`` (src/transforms/graph.py:67-96,
+    src/data/data.py:481-586, src/utils/graph.py:466-502) and the forward-star arrays of
+    ``CutPursuitPartition._process`` (src/transforms/partition.py:190-196), in four kernel
+    passes over the table (``csrc/adjacency.hip``) instead of an edge list, a ``unique``, a
+    ``lstsq`` and a ``coalesce`` sort.
+
+    ``neighbor_index`` [N, K] int64 (any negative entry = missing), ``neighbor_distance`` [N, K]
+    f32 (may be None when ``w <= 0``); the first ``k <= K`` columns are read in place.  Edge
+    weights are ``1 / (w + d / mean(d))`` or 1 (``w <= 0``).  Nodes that no directed edge touches
+    get edges to their ``k_isolated`` nearest other nodes (``pos`` [N, 3] required then; ``batch``
+    keeps the search within a cloud), weighted by the least-squares line of weight against
+    end-point distance - closed form on five f64 sums, where the reference calls ``lstsq``.  Then
+    edges are flipped to i < j, self loops dropped and both directions of a pair merged with
+    ``reduce`` ('mean', 'add' / 'sum', 'min', 'max').  When the table holds no edge at all the
+    graph has no ``edge_attr`` (data.py:492-494, 526-528).
+
+    Returns a ``PartitionGraph``.  ``source_csr`` / ``edge_index[1]`` / identity restate what
+    ``grid_graph.edge_list_to_forward_star`` returns for sorted input; that package is
+    third-party and unpinned here.
+
+    A table whose rows name a neighbour twice (oversampled neighbourhoods) cannot be trimmed by
+    look-up: the kernels report it and the same result is computed through ``coalesce``, as it
+    is for CPU tensors."""
+    if reduce not in _REDUCE_CODES:
+        raise ValueError(f"reduce must be one of {sorted(_REDUCE_CODES)}, got {reduce!r}")
+    if neighbor_index.dim() != 2 or neighbor_index.dtype != torch.long:
+        raise ValueError("neighbor_index must be an [N, K] int64 tensor")
+    N, K = neighbor_index.shape
+    k, k_isolated = int(k), int(k_isolated)
+    if not 1 <= k <= K:
+        raise ValueError(f"k must be in [1, {K}], got {k}")
+    if k_isolated < 0:
+        raise ValueError("k_isolated must be >= 0")
+    w = float(w)
+    if w > 0 and neighbor_distance is None:
+        raise ValueError("w > 0 needs neighbor_distance")
+    if neighbor_distance is not None and neighbor_distance.shape != neighbor_index.shape:
+        raise ValueError("neighbor_distance must have neighbor_index's shape")
+    args = (neighbor_index, neighbor_distance, k, w, pos, k_isolated, reduce, batch)
+    if not neighbor_index.is_cuda:
+        return _partition_adjacency_torch(*args)
+    _lib.require_cuda(neighbor_distance, pos, batch)
+    if k > 64 or k_isolated > 64:
+        return _partition_adjacency_torch(*args)
+    from .ops import _workspace
+    L = _lib.lib
+    dev = neighbor_index.device
+    # the table is read where it lies: knn_1's result is columns 1 .. K of a [N, K + 1] search
+    nn, dist = neighbor_index, None
+    if w > 0:
+        dist = neighbor_distance if neighbor_distance.dtype == torch.float32 else neighbor_distance.float()
+
+    def pitched(t):
+        return t is None or (t.stride(1) == 1 and t.stride(0) >= K) or N <= 1
+    if not (pitched(nn) and pitched(dist) and (dist is None or N <= 1 or dist.stride(0) == nn.stride(0))):
+        nn, dist = nn.contiguous(), None if dist is None else dist.contiguous()
+    ld = max(int(nn.stride(0)), K) if N > 1 else K
+    stream = _lib.stream_ptr(dev)
+
+    # pass A: mean distance, linked flags, repeated-neighbour check, isolated count
+    linked = torch.empty(max(N, 1), dtype=torch.uint8, device=dev)
+    stats = torch.empty(8, dtype=torch.float64, device=dev)
+    nb_stats = L.spt_adjacency_stats_workspace_bytes(N)
+    ws = _workspace(nb_stats, dev)
+    with torch.cuda.device(dev):
+        st = L.spt_adjacency_stats(_lib.ptr(nn), _lib.ptr(dist), N, ld, k, _lib.ptr(linked),
+                                   _lib.ptr(stats), _lib.ptr(ws), ws.numel(), stream)
+    _lib.check(st, "spt_adjacency_stats")
+    n_valid, sum_d, n_iso, flags = stats[:4].tolist()           # host sync (the reference's masks)
+    n_valid, n_iso, flags = int(n_valid), int(n_iso), int(flags)
+    if flags & 2:
+        raise ValueError(f"neighbor_index holds entries >= N = {N}")
+    if flags & 1:
+        return _partition_adjacency_torch(*args)
+    weighted = n_valid > 0
+    mean = float(torch.tensor(sum_d / n_valid, dtype=torch.float64).float()) if (w > 0 and weighted) else 1.0
+
+    iso_index = iso_nn = iso_w = None
+    rows_iso = 0
+    if k_isolated > 0 and n_iso > 0:
+        if pos is None:
+            raise ValueError("isolated nodes need pos to be connected")
+        posf = pos.detach().float().contiguous()
+        iso_index = torch.nonzero(linked[:N] == 0).view(-1)
+        iso_nn, iso_d = _isolated_edges(posf, iso_index, k_isolated, batch)
+        rows_iso = iso_index.numel()
+        if weighted:
+            sums = torch.empty(4, dtype=torch.float64, device=dev)
+            ws = _workspace(nb_stats, dev)
+            with torch.cuda.device(dev):
+                st = L.spt_adjacency_regression(_lib.ptr(nn), _lib.ptr(dist), _lib.ptr(posf), N, ld,
+                                                k, w, mean, _lib.ptr(sums), _lib.ptr(ws),
+                                                ws.numel(), stream)
+            _lib.check(st, "spt_adjacency_regression")
+            a, b = _regression_line(float(n_valid), *sums.tolist())
+            iso_w = (iso_d * torch.tensor(a, dtype=torch.float32, device=dev)
+                     + torch.tensor(b, dtype=torch.float32, device=dev)).contiguous()   # data.py:556
+
+    # pass B: surviving entries, counts per smaller end point, scan
+    keep = torch.empty(max(N + rows_iso, 1), dtype=torch.int64, device=dev)
+    row_start = torch.empty(N + 1, dtype=torch.int32, device=dev)
+    ws = _workspace(L.spt_adjacency_count_workspace_bytes(N), dev)
+    with torch.cuda.device(dev):
+        st = L.spt_adjacency_count(_lib.ptr(nn), N, ld, k, _lib.ptr(linked), _lib.ptr(iso_index),
+                                   _lib.ptr(iso_nn), rows_iso, k_isolated, _lib.ptr(keep),
+                                   _lib.ptr(row_start), _lib.ptr(ws), ws.numel(), stream)
+    _lib.check(st, "spt_adjacency_count")
+    E = int(row_start[N]) & 0xFFFFFFFF                            # host sync: output size
+
+    # pass C: fill, per-row sort, emit
+    edge_index = torch.empty((2, E), dtype=torch.int64, device=dev)
+    edge_attr = torch.empty(E, dtype=torch.float32, device=dev) if weighted else None
+    source_csr = torch.empty(N + 1, dtype=torch.int64, device=dev)
+    nbytes = L.spt_adjacency_fill_workspace_bytes(N, E)
+    ws = _workspace(nbytes, dev)
+    with torch.cuda.device(dev):
+        st = L.spt_adjacency_fill(_lib.ptr(nn), _lib.ptr(dist), N, ld, k, w, mean, _lib.ptr(linked),
+                                  _lib.ptr(iso_index), _lib.ptr(iso_nn), _lib.ptr(iso_w), rows_iso,
+                                  k_isolated, _REDUCE_CODES[reduce], _lib.ptr(keep),
+                                  _lib.ptr(row_start), E, _lib.ptr(edge_index), _lib.ptr(edge_attr),
+                                  _lib.ptr(source_csr), _lib.ptr(ws), ws.numel(), stream)
+    _lib.check(st, "spt_adjacency_fill")
+    return PartitionGraph(edge_index, edge_attr, source_csr, n_iso)

@@ -10,7 +10,7 @@ from . import _lib
 __all__ = ["horizontal_edge_features", "EDGE_FEATURE_COLUMNS", "NodeSize", "SampleSubNodes",
            "SampleSegments", "SampleEdges", "OnTheFlyHorizontalEdgeFeatures",
            "SampleRadiusSubgraphs", "OnTheFlyInstanceGraph", "segment_sampling_weights",
-           "NAGRestrictSize", "MortonOrder", "morton_code"]
+           "NAGRestrictSize", "MortonOrder", "morton_code", "PartitionAdjacency"]
 
 EDGE_FEATURE_COLUMNS = [
     "mean_off_x", "mean_off_y", "mean_off_z", "std_off_x", "std_off_y", "std_off_z",
@@ -79,6 +79,29 @@ def vertical_edge_features(child, parent):
             _lib.ptr(out), _lib.stream_ptr(dev))
     _lib.check(st, "spt_vertical_edge_features_f32")
     return out
+
+
+class PartitionAdjacency:
+    """The three reference steps ``AdjacencyGraph(k, w)`` -> ``ConnectIsolated(k_isolated)`` ->
+    ``Data.to_trimmed(reduce)`` (src/transforms/graph.py:45-96, 1455-1472, src/data/data.py:
+    563-586; the last one opens ``CutPursuitPartition._process``, src/transforms/partition.py:141)
+    fused into ``graph.partition_adjacency``: takes a ``Data`` with ``neighbor_index`` /
+    ``neighbor_distance`` / ``pos`` (and ``batch`` if present), returns it with the trimmed,
+    (i, j)-sorted ``edge_index`` / ``edge_attr`` and ``edge_source_csr`` [N + 1], the forward
+    star's row pointers (``edge_index[1]`` is its target array)."""
+
+    def __init__(self, k=10, w=-1, k_isolated=1, reduce="mean"):
+        self.k, self.w, self.k_isolated, self.reduce = k, w, k_isolated, reduce
+
+    def __call__(self, data):
+        from .graph import partition_adjacency
+        if data.neighbor_index is None:
+            raise ValueError("PartitionAdjacency needs data.neighbor_index (run the kNN first)")
+        g = partition_adjacency(data.neighbor_index, data.get("neighbor_distance"), self.k, w=self.w,
+                                pos=data.get("pos"), k_isolated=self.k_isolated, reduce=self.reduce,
+                                batch=data.get("batch"))
+        data.edge_index, data.edge_attr, data.edge_source_csr = g.edge_index, g.edge_attr, g.source_csr
+        return data
 
 
 # ---------------------------------------------------------------------------
