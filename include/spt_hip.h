@@ -433,8 +433,10 @@ int spt_edge_attn_bwd_acc_f32(const float* qkv, int64_t n, int H, int D, int Dv,
  * 2.8 ms for one level-1 call): the per-edge [dk | dv] rows are streamed to the workspace in CSR
  * order and summed per target through (tperm, trowptr) = spt_csr_build(tgt_sorted, e, n) - a CSR
  * view of the TARGETS over the CSR positions, built once per batch and level - in a fixed order
- * (deterministic).  It needs the scratch of spt_edge_attn_bwd_ex_workspace_bytes(n, e, ...)
- * (per-node rows + 512 B per edge), that view, and optionally src_sorted [e] int32 =
+ * (deterministic); dq of a node whose edges lie in several tiles is summed in ascending tile order
+ * by the same pass (two 256 B slots per tile), so no sum depends on the order the waves run in.
+ * It needs the scratch of spt_edge_attn_bwd_ex_workspace_bytes(n, e, ...)
+ * (per-node rows + 512 B per edge + 512 B per tile), that view, and optionally src_sorted [e] int32 =
  * edge_index[0] in CSR order (NULL: rebuilt from erowptr).  Without the view or the workspace the
  * packed kernel runs instead.
  * With gedge_attr_accumulate == 0 the edge-lane kernel zero-fills gedge_attr first (both waves of

@@ -30,6 +30,12 @@
 //     contiguous per tile) and summed per target by attn_kv_reduce_kernel through a CSR view of
 //     the TARGETS (built once per batch and level like the source view): deterministic, f32
 //     exact per edge, and ~3x cheaper than the atomics.
+//   * dq in a fixed order too.  A tile adds the dq of a node that lies wholly inside it to the
+//     zeroed row (one add: order-free); the dq of its first and last node - which may go on in
+//     other tiles, owned by other wave pairs - goes to two 256-byte slots per tile, which the
+//     same reduction pass adds per node in ascending tile order (tests/test_reproducible_gpu.py,
+//     tests/test_capture_gpu.py: a node of 18+ edges used to collect three or more float atomics
+//     in the order its pairs happened to run).
 //   * nothing in the loop is a register-returning global load: tile data, per-edge node rows and
 //     tile ids all arrive by LDS-DMA (ids two tiles ahead, edge_attr one tile ahead, the gathered
 //     rows refilled as soon as the tile's per-edge math has consumed them), waited for with
@@ -178,7 +184,7 @@ __device__ __forceinline__ float qk_scale_of(int mode, float a, int deg) {
 //   dm[node][hh][g][{delta(bl=0), delta(bl=1), ml(bl=0), ml(bl=1)}],  head = 4 (2 hh + bl) + g
 //     delta = <gout, out> of the head, ml = m + log(z + 1e-16) (softmax weight = exp(p - ml))
 //   qs[node][64] = q * qk-scale of the node,  scl[node] = that scale (0 for a node without edges)
-// One thread per (node, head).  Also zero-fills the q columns of gqkv (dq arrives by atomics).
+// One thread per (node, head).  Also zero-fills the q columns of gqkv (the main kernel adds dq there).
 __global__ __launch_bounds__(256) void attn_bwd_prep_kernel(
     const float* __restrict__ qkv, const float* __restrict__ gout, const float* __restrict__ out,
     const float* __restrict__ m, const float* __restrict__ z, const int32_t* __restrict__ erowptr,
@@ -232,10 +238,13 @@ __global__ __launch_bounds__(256) void pack_tile_ids_kernel(
 // (tperm / trowptr = CSR view of the targets over the CSR-by-source positions; stable sort ->
 // a fixed summation order -> deterministic).  Half a wave per target node: 32 lanes x 16 bytes =
 // one 512-byte row per load, eight rows in flight.  The same pass applies the node's qk scale to
-// the q columns (the main kernel adds the unscaled dq of the node's edges).
+// the q columns, after adding the node's rows of dqb in ascending tile order: slot 0 of a tile =
+// dq of its first node, slot 1 = of its last node when that is another one (erowptr = the CSR
+// view by source, E edges; the main kernel added the dq of every other node to gqkv itself).
 __global__ __launch_bounds__(256) void attn_kv_reduce_kernel(
     const float* __restrict__ dkv, const int32_t* __restrict__ tperm,
-    const int32_t* __restrict__ trowptr, const float* __restrict__ scl, int64_t N,
+    const int32_t* __restrict__ trowptr, const float* __restrict__ scl,
+    const int32_t* __restrict__ erowptr, const float* __restrict__ dqb, int64_t E, int64_t N,
     float* __restrict__ gqkv) {
   const int lane = threadIdx.x & 31;
   const int64_t half = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 5;
@@ -269,7 +278,20 @@ __global__ __launch_bounds__(256) void attn_kv_reduce_kernel(
     *reinterpret_cast<f32x4*>(gqkv + t * LD + 64 + 4 * lane) = acc;
     if (lane < 16) {          // the q columns hold the unscaled sum of dq over the node's edges
       f32x4* qp = reinterpret_cast<f32x4*>(gqkv + t * LD + 4 * lane);
-      *qp = *qp * scl[t];
+      f32x4 q = *qp;
+      const int64_t ea = erowptr[t], eb = erowptr[t + 1];
+      if (eb > ea) {
+        const int64_t t0 = ea / TE, t1 = (eb - 1) / TE;
+        for (int64_t tt = t0; tt <= t1; ++tt) {
+          int slot = 0;                              // first node of the tile
+          if (tt == t0 && ea % TE != 0) {
+            if (eb < (tt + 1) * TE && eb != E) break;   // neither first nor last: added in place
+            slot = 1;
+          }
+          q += *reinterpret_cast<const f32x4*>(dqb + (tt * 2 + slot) * 64 + 4 * lane);
+        }
+      }
+      *qp = q * scl[t];
     }
   }
 }
@@ -309,7 +331,8 @@ __global__ __launch_bounds__(WAVES * 64, 2) void attn_bwd_el_kernel(
     const float* __restrict__ bk, const float* __restrict__ Wq, const float* __restrict__ bq,
     const float* __restrict__ Wv, const float* __restrict__ bv, const float* __restrict__ dm,
     const float* __restrict__ qs, const float* __restrict__ gout, float* __restrict__ gqkv,
-    float* __restrict__ gea, int gea_acc, float* __restrict__ dkv, float* __restrict__ partial) {
+    float* __restrict__ gea, int gea_acc, float* __restrict__ dkv, float* __restrict__ dqb,
+    float* __restrict__ partial) {
   static_assert(PREC == 1 || PREC == 3, "bf16 matrix pipe only");
   constexpr bool LO = PREC == 3;
   __shared__ __attribute__((aligned(16))) float lds_wave[WAVES][L_END];
@@ -762,13 +785,25 @@ __global__ __launch_bounds__(WAVES * 64, 2) void attn_bwd_el_kernel(
         }
       }
       // dq of the tile's nodes, unscaled (the reduction pass applies the node's qk scale); the
-      // only data-dependent memory instructions: issued last
+      // only data-dependent memory instructions: issued last.  A node between the tile's first and
+      // last one has all its edges in this tile: its one add meets the zero the prep kernel wrote.
+      // The first and the last node may go on in other tiles (other pairs; a node of more than 17
+      // edges in three or more): an add per tile would sum in the order the pairs happen to run,
+      // so their rows go to the tile's two slots of dqb and the reduction pass adds them in
+      // ascending tile order.
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        if (4 * g + r < nn) {
-          float* row = gqkv + (int64_t)nd4[r] * LD + 32 * hh + c;
+        const int rk = 4 * g + r;
+        if (rk < nn) {
+          if (rk == 0 || rk == nn - 1) {
+            float* row = dqb + (t * 2 + (rk == 0 ? 0 : 1)) * 64 + 32 * hh + c;
 #pragma unroll
-          for (int bl = 0; bl < NBW; ++bl) unsafeAtomicAdd(row + 16 * bl, Cn[bl][r]);
+            for (int bl = 0; bl < NBW; ++bl) row[16 * bl] = Cn[bl][r];
+          } else {
+            float* row = gqkv + (int64_t)nd4[r] * LD + 32 * hh + c;
+#pragma unroll
+            for (int bl = 0; bl < NBW; ++bl) unsafeAtomicAdd(row + 16 * bl, Cn[bl][r]);
+          }
         }
       }
       if (!leader) flag_set(flg + F_DONE, k + 1);
@@ -822,7 +857,7 @@ size_t attn_bwd_el_workspace_bytes(int64_t n, int64_t e) {
   const size_t ntiles = (ee + el::TE - 1) / el::TE;
   return align_up((size_t)n * 32 * 4, 256) + align_up((size_t)n * 64 * 4, 256) +
          align_up((size_t)n * 4, 256) + align_up(ee * 4, 256) + align_up(ntiles * 48 * 4, 256) +
-         align_up(ee * 128 * 4, 256);
+         align_up(ee * 128 * 4, 256) + align_up(ntiles * 2 * 64 * 4, 256);
 }
 
 // returns the number of partial tables written (<= ATTN_EL_MAX_PAIRS).  gqkv needs no
@@ -857,6 +892,8 @@ int attn_bwd_el_launch(const float* qkv, int64_t n, const int32_t* erowptr, cons
   int32_t* ids3 = (int32_t*)w;
   w += align_up((size_t)ntiles * 48 * 4, 256);
   float* dkv = (float*)w;
+  w += align_up((size_t)(e > 0 ? e : 1) * 128 * 4, 256);
+  float* dqb = (float*)w;                     // [ntiles][2][64]: dq of a tile's first / last node
   el::attn_bwd_prep_kernel<<<(int)ceil_div(n * 16, 256), 256, 0, stream>>>(
       qkv, gout, out, m, z, erowptr, n, scale_mode, scale_a, dm, qs, scl, gqkv);
   if (!tile_ids) {
@@ -874,7 +911,7 @@ int attn_bwd_el_launch(const float* qkv, int64_t n, const int32_t* erowptr, cons
 #define SPT_EL_LAUNCH(P, F)                                                                      \
   el::attn_bwd_el_kernel<P, F><<<grid, el::WAVES * 64, 0, stream>>>(                             \
       qkv, e, tile_ids, ntiles, tpw, ea, Wk, bk, Wq, bq, Wv, bv, dm, qs, gout, gqkv, gea, gea_acc, \
-      dkv, partial)
+      dkv, dqb, partial)
   if (prec == 3) {
     if (g_attn_el_full_line) SPT_EL_LAUNCH(3, true); else SPT_EL_LAUNCH(3, false);
   } else {
@@ -883,7 +920,7 @@ int attn_bwd_el_launch(const float* qkv, int64_t n, const int32_t* erowptr, cons
 #undef SPT_EL_LAUNCH
   const int64_t rblocks = ceil_div(n, (int64_t)8);
   el::attn_kv_reduce_kernel<<<(int)(rblocks < 256 * 16 ? rblocks : 256 * 16), 256, 0, stream>>>(
-      dkv, tperm, trowptr, scl, n, gqkv);
+      dkv, tperm, trowptr, scl, erowptr, dqb, e, n, gqkv);
   return grid * (el::WAVES / 2);
 }
 

@@ -252,6 +252,7 @@ class SPTTrainStep:
 
     _timed_steps = 0
     graph = None                      # a captured step (capture()): replayed by step()
+    _graph_keep = None                # the scratch / constant tensors whose addresses the graph holds
     criterion = targets = None        # the default loss: plain CE on `labels`
 
     def _fwd_bwd(self):
@@ -317,19 +318,26 @@ class SPTTrainStep:
         paused = _ops.pause_timers(True)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
+        # The kernels take the scratch buffers and constant tables of `ops` as raw addresses: the
+        # graph reads them without a reference, while ops._CONST is cleared past 512 keys and a
+        # stream's scratch is replaced when a larger one is asked for (an eager validation pass on
+        # other batch shapes does both).  Everything handed out from the first warm-up step to the
+        # end of the capture is kept here, for as long as the graph lives.
+        self._graph_keep = []
         try:
-            with torch.cuda.stream(side):
-                for _ in range(warmup):                # allocator, workspaces, optimizer state
-                    self._fwd_bwd()
+            with _ops.keep_handed_out(self._graph_keep):
+                with torch.cuda.stream(side):
+                    for _ in range(warmup):            # allocator, workspaces, optimizer state
+                        self._fwd_bwd()
+                        if self._graph_opt:
+                            self.opt.step()
+                torch.cuda.current_stream(dev).wait_stream(side)
+                torch.cuda.synchronize(dev)
+                self.graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):
+                    loss = self._fwd_bwd()
                     if self._graph_opt:
                         self.opt.step()
-            torch.cuda.current_stream(dev).wait_stream(side)
-            torch.cuda.synchronize(dev)
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):
-                loss = self._fwd_bwd()
-                if self._graph_opt:
-                    self.opt.step()
             self._graph_loss = loss
             # the gradient tensors autograd allocated inside the capture: the replay writes THESE
             self._graph_grads = [p.grad for p in self.params]

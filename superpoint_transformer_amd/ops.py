@@ -6,6 +6,7 @@ stream; there is no eager-PyTorch path.  The one exception is the criterion
 CPU tensors and heads wider than 32 classes take a torch composition of the
 same closed forms, so that criterion and metric modules also run off the device.
 """
+import contextlib
 import ctypes
 import os
 
@@ -61,6 +62,28 @@ def pause_timers(on=True):
 
 
 _CONST = {}
+_KEEP = []           # the lists of the active keep_handed_out() blocks, innermost last
+
+
+@contextlib.contextmanager
+def keep_handed_out(into):
+    """Inside the block every tensor that ``_const_tensor`` or ``_workspace`` hands out is also
+    appended to the list ``into`` (once).  Kernels get these tensors as raw addresses, so a captured
+    graph reads them without holding a reference, while ``_CONST`` is cleared past 512 keys and a
+    stream's scratch is replaced when a larger one is asked for: whoever captures keeps ``into``
+    for as long as the graph lives (``hotpath.SPTTrainStep.capture``)."""
+    _KEEP.append(into)
+    try:
+        yield into
+    finally:
+        _KEEP.pop()
+
+
+def _handed_out(t):
+    for kept in _KEEP:
+        if not any(t is u for u in kept):
+            kept.append(t)
+    return t
 
 
 def _const_tensor(vals, dtype, dev):
@@ -73,7 +96,7 @@ def _const_tensor(vals, dtype, dev):
         if len(_CONST) > 512:
             _CONST.clear()
         t = _CONST[key] = torch.tensor(list(vals), dtype=dtype, device=dev)
-    return t
+    return _handed_out(t)
 
 
 class _timed:
@@ -384,7 +407,7 @@ def _workspace(nbytes, dev):
     if buf is None or buf.numel() < nbytes:
         buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=dev)
         _WS[key] = buf
-    return buf
+    return _handed_out(buf)
 
 
 class _GraphNorm(torch.autograd.Function):

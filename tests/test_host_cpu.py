@@ -246,3 +246,26 @@ def test_product_ops_refuse_cpu_tensors_loudly():
             call()
     with pytest.raises(ValueError, match="k \\+ 1 <= 64"):
         NB.knn_1_features(xyz, 64, 0.5)
+
+
+def test_keep_handed_out_records_constant_tables_past_the_cache_clear():
+    """``ops.keep_handed_out`` (what ``SPTTrainStep.capture`` wraps its warm-up and capture in):
+    every table handed out inside the block is recorded once, nested blocks each get their own
+    record, nothing is recorded outside, and the record keeps a table alive when ``_CONST`` is
+    cleared past 512 keys."""
+    from superpoint_transformer_amd import ops
+    dev = torch.device("cpu")
+    keep, inner = [], []
+    with ops.keep_handed_out(keep):
+        a = ops._const_tensor([1, 2], torch.int64, dev)
+        assert ops._const_tensor([1, 2], torch.int64, dev) is a
+        ops._const_tensor([3], torch.int32, dev)
+        with ops.keep_handed_out(inner):
+            d = ops._const_tensor([4], torch.int32, dev)
+    ops._const_tensor([5], torch.int32, dev)
+    assert len(keep) == 3 and keep[0] is a and keep[2] is d
+    assert len(inner) == 1 and inner[0] is d and not ops._KEEP
+    for i in range(600):
+        ops._const_tensor([1000 + i], torch.int64, dev)
+    assert len(ops._CONST) < 600                       # the cache was cleared on the way
+    assert ops._const_tensor([1, 2], torch.int64, dev) is not a and keep[0].tolist() == [1, 2]
