@@ -733,6 +733,59 @@ int spt_adjacency_fill(const int64_t* neighbors, const float* distances, int64_t
                        size_t ws_bytes, spt_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * GroundElevation: ground filters, RANSAC plane, elevation
+ * GroundElevation._process (src/transforms/point.py:268-326) with model 'ransac': the three
+ * filters of src/utils/ground.py:25-97 (xy_partition: src/utils/partition.py:17-50), the plane
+ * of single_plane_model's CPU branch (ground.py:116-131: RANSACRegressor(residual_threshold) on
+ * (xy, z), vertical residual, final least-squares fit on the inliers) and the elevation.
+ * pos [n, 3] f32, one cloud, 1 <= n < 2^31.
+ *
+ * spt_ground_bounds_f32: bounds = 5 device floats: min z, then min and max of trunc(x / grid)
+ *   and min and max of trunc(y / grid) (whole numbers; IEEE f32 division, truncation toward
+ *   zero, exactly torch's div(..., rounding_mode='trunc')); grid <= 0: min z only, the rest 0.
+ * spt_ground_cell_min_f32: table [num_i * num_j] u64, cell (i - i_min) * num_j + (j - j_min):
+ *   (order-preserving bits of z) << 32 | index of the lowest point of the cell, all ones for an
+ *   empty cell; among equal z (-0.0 == +0.0) the lowest index wins.  Every point takes part
+ *   (ground.py:45-71 runs on the whole cloud).  A point outside the table is skipped.
+ * spt_ground_trim_f32: index [capacity] int64 = the points with z - bounds[0] < z_threshold
+ *   (use_z) and verticality < verticality_threshold (verticality [n] non-NULL) that are the
+ *   winner of their cell (table non-NULL), in increasing point order; *count (device int64) =
+ *   their number M, never above capacity.  ws: spt_ground_trim_workspace_bytes(n).
+ * spt_ground_ransac_f32: num_hypotheses <= 256 triplets of trimmed points, either
+ *   idx = min(floor(u M), M - 1) from u [H, 3] f32 in [0, 1) or samples [H, 3] int64 given
+ *   (exactly one non-NULL); M = *count is read on the device.  counts [H] int32 = number of
+ *   trimmed points with |z - (a x + b y + c)| < residual_threshold for the plane through the
+ *   triplet (f64 arithmetic), -1 for a triplet with a repeated or out-of-range index or a
+ *   triangle degenerate in XY.  status = 8 device doubles: M, best count, best hypothesis
+ *   (largest count, lowest index among equals; -1: none valid), a, b, c of the least-squares
+ *   plane of the best hypothesis's inliers (f64 moments, per-workgroup partials summed in a
+ *   fixed order), number of valid hypotheses, number of inliers refitted (-1: inliers
+ *   rank-deficient, (a, b, c) is the hypothesis's own plane).  Bitwise reproducible.
+ * spt_ground_elevation_f32: elevation [n] = (z - (a x + b y + c)) / scale, plane read from
+ *   status on the device, f64 arithmetic rounded once.
+ * ---------------------------------------------------------------------- */
+size_t spt_ground_bounds_workspace_bytes(int64_t num_points);
+int spt_ground_bounds_f32(const float* pos, int64_t num_points, float grid, float* bounds,
+                          void* ws, size_t ws_bytes, spt_stream_t stream);
+int spt_ground_cell_min_f32(const float* pos, int64_t num_points, float grid, int64_t i_min,
+                            int64_t j_min, int64_t num_i, int64_t num_j, uint64_t* table,
+                            spt_stream_t stream);
+size_t spt_ground_trim_workspace_bytes(int64_t num_points);
+int spt_ground_trim_f32(const float* pos, int64_t num_points, const float* bounds, int use_z,
+                        float z_threshold, const float* verticality, float verticality_threshold,
+                        const uint64_t* table, int64_t num_cells, int64_t* index,
+                        int64_t capacity, int64_t* count, void* ws, size_t ws_bytes,
+                        spt_stream_t stream);
+size_t spt_ground_ransac_workspace_bytes(int num_hypotheses);
+int spt_ground_ransac_f32(const float* pos, int64_t num_points, const int64_t* index,
+                          const int64_t* count, int64_t capacity, const float* u,
+                          const int64_t* samples, int num_hypotheses, double residual_threshold,
+                          int32_t* counts, double* status, void* ws, size_t ws_bytes,
+                          spt_stream_t stream);
+int spt_ground_elevation_f32(const float* pos, int64_t num_points, const double* status,
+                             float scale, float* elevation, spt_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * NAG selection / re-indexing                                             (f3)
  * The integer work of NAG.select (src/data/nag.py:306-399), Data.select
  * (src/data/data.py:286-470) and Cluster.select (src/data/cluster.py:79-140).  All ids

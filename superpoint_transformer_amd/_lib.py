@@ -18,6 +18,7 @@ _int = _c.c_int
 _p = _c.c_void_p
 _sz = _c.c_size_t
 _f32 = _c.c_float
+_f64 = _c.c_double
 
 # name -> (restype, argtypes).  Must list EVERY symbol of include/spt_hip.h:
 # tests/test_abi.py parses the header and checks both directions.
@@ -228,6 +229,14 @@ SIGNATURES = {
     "spt_adjacency_fill_workspace_bytes": (_sz, [_i64, _i64]),
     "spt_adjacency_fill": (_int, [_p, _p, _i64, _i64, _int, _f32, _f32, _p, _p, _p, _p, _i64, _int, _int,
                                   _p, _p, _i64, _p, _p, _p, _p, _sz, _p]),
+    "spt_ground_bounds_workspace_bytes": (_sz, [_i64]),
+    "spt_ground_bounds_f32": (_int, [_p, _i64, _f32, _p, _p, _sz, _p]),
+    "spt_ground_cell_min_f32": (_int, [_p, _i64, _f32, _i64, _i64, _i64, _i64, _p, _p]),
+    "spt_ground_trim_workspace_bytes": (_sz, [_i64]),
+    "spt_ground_trim_f32": (_int, [_p, _i64, _p, _int, _f32, _p, _f32, _p, _i64, _p, _i64, _p, _p, _sz, _p]),
+    "spt_ground_ransac_workspace_bytes": (_sz, [_int]),
+    "spt_ground_ransac_f32": (_int, [_p, _i64, _p, _p, _i64, _p, _p, _int, _f64, _p, _p, _p, _sz, _p]),
+    "spt_ground_elevation_f32": (_int, [_p, _i64, _p, _f32, _p, _p]),
 }
 
 

@@ -10,7 +10,7 @@ from . import _lib
 __all__ = ["horizontal_edge_features", "EDGE_FEATURE_COLUMNS", "NodeSize", "SampleSubNodes",
            "SampleSegments", "SampleEdges", "OnTheFlyHorizontalEdgeFeatures",
            "SampleRadiusSubgraphs", "OnTheFlyInstanceGraph", "segment_sampling_weights",
-           "NAGRestrictSize", "MortonOrder", "morton_code", "PartitionAdjacency"]
+           "NAGRestrictSize", "MortonOrder", "morton_code", "PartitionAdjacency", "GroundElevation"]
 
 EDGE_FEATURE_COLUMNS = [
     "mean_off_x", "mean_off_y", "mean_off_z", "std_off_x", "std_off_y", "std_off_z",
@@ -101,6 +101,60 @@ class PartitionAdjacency:
                                 pos=data.get("pos"), k_isolated=self.k_isolated, reduce=self.reduce,
                                 batch=data.get("batch"))
         data.edge_index, data.edge_attr, data.edge_source_csr = g.edge_index, g.edge_attr, g.source_csr
+        return data
+
+
+class GroundElevation:
+    """``GroundElevation`` of the preprocessing chain (src/transforms/point.py:185-326,
+    configs/datamodule/semantic/default.yaml between PointFeatures and AdjacencyGraph): takes a
+    ``Data`` with ``pos`` [N, 3] f32 of ONE cloud on the device and returns it with
+    ``elevation`` [N, 1], the height above a RANSAC ground plane divided by ``scale``
+    (``ground.ground_elevation`` on ``csrc/ground.hip``).
+
+    ``z_threshold`` / ``verticality_threshold`` / ``xy_grid`` select the reference's three
+    filters; ``verticality_threshold`` needs ``data.verticality`` (``PointFeatures``).
+    ``scale <= 0`` skips the transform.  ``model`` 'knn' and 'mlp' are not built.  ``kwargs``:
+    ``random_state`` (seed of the hypotheses, default 0), ``residual_threshold`` (default 1e-3)
+    as ``single_plane_model`` takes them, and ``num_hypotheses`` (default 100); others are
+    dropped like the reference's ``filter_kwargs`` does.  The fit's record is kept as
+    ``ground_plane_``."""
+
+    _KWARGS = ("random_state", "residual_threshold", "num_hypotheses")
+
+    def __init__(self, z_threshold=None, verticality_threshold=None, xy_grid=None, model="ransac",
+                 scale=3.0, **kwargs):
+        if verticality_threshold is not None:
+            assert 0 < verticality_threshold < 1
+        if xy_grid is not None:
+            assert xy_grid > 0
+        assert model in ["ransac", "knn", "mlp"]
+        self.z_threshold, self.verticality_threshold, self.xy_grid = \
+            z_threshold, verticality_threshold, xy_grid
+        self.model, self.scale, self.kwargs = model, scale, kwargs
+        self.ground_plane_ = None
+
+    def __call__(self, data):
+        from .ground import ground_elevation
+        if self.scale <= 0:
+            return data
+        if self.model != "ransac":
+            raise NotImplementedError(
+                f"GroundElevation(model={self.model!r}) is not implemented: only 'ransac' is")
+        verticality = None
+        if self.verticality_threshold and (0 < self.verticality_threshold < 1):
+            verticality = data.get("verticality")
+            if verticality is None:
+                raise ValueError(
+                    "The Data object does not have a 'verticality' attribute. "
+                    "To compute verticality, please call PointFeatures on "
+                    "your Data first")
+        kw = {k: v for k, v in self.kwargs.items() if k in self._KWARGS}
+        elevation, plane = ground_elevation(
+            data.pos, z_threshold=self.z_threshold, verticality=verticality,
+            verticality_threshold=self.verticality_threshold if verticality is not None else None,
+            xy_grid=self.xy_grid, scale=self.scale, **kw)
+        data.elevation = elevation
+        self.ground_plane_ = plane
         return data
 
 
