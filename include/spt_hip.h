@@ -786,6 +786,38 @@ int spt_ground_elevation_f32(const float* pos, int64_t num_points, const double*
                              float scale, float* elevation, spt_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * PointFeatures: colour keys and density                  (csrc/point_feat.hip)
+ * PointFeatures._process (src/transforms/point.py:116-182): to_float_rgb (src/utils/color.py:
+ * 17-22), rgb2hsv and rgb2lab (src/utils/features.py:8-86) with the / 360 of the hue and the
+ * / 100 of lab, and density = k_n / dmax_n^2 (point.py:158-161).
+ *
+ * spt_point_color_f32: rgb [n, 3] contiguous, uint8 (rgb_is_u8) or f32.  keys: bit 0 rgb as
+ *   [0, 1] floats, bit 1 hsv, bit 2 lab; each selected output is [n, 3] f32 written at
+ *   out[i * ld + c], c < 3: ld = 3 for a tensor of its own, ld = F and out = table + column for
+ *   a block of a wider [n, F] table.  The values do not depend on ld or on alignment.  The
+ *   colours are divided by 255 when some value is > 1 (decided on the device, no host read;
+ *   a NaN anywhere: not divided, as rgb.max() > 1 is False) and clamped to [0, 1].  hsv: the
+ *   reference's f32 operations in its order, IEEE division; hue = (h2, h3, h1)[argmin], first
+ *   minimal channel on ties, / 360 (grey 0.5, [9, 5, 5] 1.0, black s = 1).  lab: sRGB
+ *   linearisation (accurate powf), x 100, matrix, round to 4 decimals, white point, cbrtf or
+ *   the linear branch, second matrix, L - 16, round to 4 decimals, / 100.  An output must not
+ *   overlap rgb.  ws: spt_point_color_workspace_bytes(n), 4-byte aligned.
+ * spt_point_density_f32: density [n] f32 = float(count of neighbor_index[i, :k] >= 0) /
+ *   (max of neighbor_distance[i, :k])^2, plain IEEE f32 (all distances -1: 0 / 1 = 0; max 0:
+ *   inf; a NaN distance: NaN).  Row i of a table starts at element i * ld (ld >= k): a column
+ *   slice of a wider table is read in place.  1 <= k <= 255.
+ * n = 0 returns 0 without a launch.
+ * ---------------------------------------------------------------------- */
+size_t spt_point_color_workspace_bytes(int64_t num_points);
+int spt_point_color_f32(const void* rgb, int rgb_is_u8, int64_t num_points, int keys,
+                        float* out_rgb, int64_t ld_rgb, float* out_hsv, int64_t ld_hsv,
+                        float* out_lab, int64_t ld_lab, void* ws, size_t ws_bytes,
+                        spt_stream_t stream);
+int spt_point_density_f32(const int64_t* neighbor_index, int64_t ld_index,
+                          const float* neighbor_distance, int64_t ld_distance,
+                          int64_t num_points, int k, float* density, spt_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * NAG selection / re-indexing                                             (f3)
  * The integer work of NAG.select (src/data/nag.py:306-399), Data.select
  * (src/data/data.py:286-470) and Cluster.select (src/data/cluster.py:79-140).  All ids

@@ -237,6 +237,9 @@ SIGNATURES = {
     "spt_ground_ransac_workspace_bytes": (_sz, [_int]),
     "spt_ground_ransac_f32": (_int, [_p, _i64, _p, _p, _i64, _p, _p, _int, _f64, _p, _p, _p, _sz, _p]),
     "spt_ground_elevation_f32": (_int, [_p, _i64, _p, _f32, _p, _p]),
+    "spt_point_color_workspace_bytes": (_sz, [_i64]),
+    "spt_point_color_f32": (_int, [_p, _int, _i64, _int, _p, _i64, _p, _i64, _p, _i64, _p, _sz, _p]),
+    "spt_point_density_f32": (_int, [_p, _i64, _p, _i64, _i64, _int, _p, _p]),
 }
 
 

@@ -289,6 +289,34 @@ class Data:
         out.num_nodes = self._num_nodes
         return out
 
+    def add_keys_to(self, keys, to="x", strict=True, delete_after=False):
+        """Concatenate the attributes ``keys``, in their order, to the columns of ``to``
+        (data.py:1097-1141): an existing ``to`` comes first, 1-D features count as one column,
+        a missing key raises when ``strict`` and is skipped otherwise, a feature whose row count
+        differs from ``to``'s (from ``num_nodes`` without a ``to``, when ``strict``) raises;
+        ``delete_after`` removes the keys.  ``None`` or no keys: nothing happens."""
+        if keys is None or len(keys) == 0:
+            return
+        previous = self.get(to)
+        feats = [] if previous is None else [previous]
+        for key in keys:
+            feat = self.get(key)
+            if feat is None:
+                if strict:
+                    raise Exception(f"Data should contain the attribute '{key}'")
+                continue
+            if delete_after:
+                self._store.pop(key, None)
+            if previous is None:
+                if strict and self.num_nodes != feat.shape[0]:
+                    raise Exception(f"Data should contain the attribute '{to}'")
+            elif previous.shape[0] != feat.shape[0]:
+                raise Exception(
+                    f"The tensors '{to}' and '{key}' can't be concatenated, "
+                    f"'{to}': {previous.shape[0]}, '{key}': {feat.shape[0]}")
+            feats.append(feat.unsqueeze(-1) if feat.dim() == 1 else feat)
+        self[to] = torch.cat(feats, dim=1)
+
     def select(self, idx, update_sub=True, update_super=True, num_sub=None, num_super=None):
         """``(data, (idx_sub, sub_super), (idx_super, super_sub))`` - data.py:286-470.
         ``num_sub`` / ``num_super``: sizes of the levels below / above when known (else

@@ -10,7 +10,8 @@ from . import _lib
 __all__ = ["horizontal_edge_features", "EDGE_FEATURE_COLUMNS", "NodeSize", "SampleSubNodes",
            "SampleSegments", "SampleEdges", "OnTheFlyHorizontalEdgeFeatures",
            "SampleRadiusSubgraphs", "OnTheFlyInstanceGraph", "segment_sampling_weights",
-           "NAGRestrictSize", "MortonOrder", "morton_code", "PartitionAdjacency", "GroundElevation"]
+           "NAGRestrictSize", "MortonOrder", "morton_code", "PartitionAdjacency", "GroundElevation",
+           "PointFeatures", "AddKeysTo"]
 
 EDGE_FEATURE_COLUMNS = [
     "mean_off_x", "mean_off_y", "mean_off_z", "std_off_x", "std_off_y", "std_off_z",
@@ -155,6 +156,48 @@ class GroundElevation:
             xy_grid=self.xy_grid, scale=self.scale, **kw)
         data.elevation = elevation
         self.ground_plane_ = plane
+        return data
+
+
+class PointFeatures:
+    """``PointFeatures`` of the preprocessing chain (src/transforms/point.py:41-182, after ``KNN``
+    in configs/datamodule/semantic/default.yaml): takes a ``Data`` on the device and returns it
+    with the requested keys among ``rgb`` / ``hsv`` / ``lab`` (from ``data.rgb``, uint8 in
+    [0, 255] or floats in [0, 1]), ``density`` (from ``neighbor_index`` / ``neighbor_distance``)
+    and the geometric keys (from ``pos`` / ``neighbor_index``); see ``features.point_features``.
+    ``keys=None``: every key of the reference's ``POINT_FEATURES``.  ``chunk_size`` is accepted
+    and ignored: nothing here is chunked."""
+
+    def __init__(self, keys=None, k_min=5, k_step=-1, k_min_search=25, add_self_as_neighbor=True,
+                 chunk_size=100000, overwrite=True):
+        from .features import POINT_FEATURES, sanitize_keys
+        self.keys = sanitize_keys(keys, default=POINT_FEATURES)
+        self.k_min, self.k_step, self.k_min_search = k_min, k_step, k_min_search
+        self.add_self_as_neighbor = add_self_as_neighbor
+        self.chunk_size = chunk_size
+        self.overwrite = overwrite
+
+    def __call__(self, data):
+        from .features import point_features
+        return point_features(data, self.keys, k_min=self.k_min, k_step=self.k_step,
+                              k_min_search=self.k_min_search,
+                              add_self_as_neighbor=self.add_self_as_neighbor,
+                              overwrite=self.overwrite)
+
+
+class AddKeysTo:
+    """``AddKeysTo`` (src/transforms/data.py:221-249): concatenates the attributes ``keys`` to
+    the columns of ``to`` with ``Data.add_keys_to``; ``AddKeysTo(keys=partition_hf, to='x',
+    delete_after=False)`` builds the ``x`` the partition reads.  ``features.partition_input``
+    is this step fused with ``PointFeatures``."""
+
+    def __init__(self, keys=None, to="x", strict=True, delete_after=True):
+        self.keys = [keys] if isinstance(keys, str) else keys
+        self.to, self.strict, self.delete_after = to, strict, delete_after
+
+    def __call__(self, data):
+        data.add_keys_to(keys=self.keys, to=self.to, strict=self.strict,
+                         delete_after=self.delete_after)
         return data
 
 
