@@ -1164,6 +1164,24 @@ int spt_fused_linear_bwd_runs_gn_f32(
     const float* xprev, int K, const float* pre_am, const float* pre_scale, const float* pre_bias,
     float pre_slope, const float* W, float* gx, float* gW, double* prev_total, int mode, void* ws,
     size_t ws_bytes, const spt_gn_bwd_tables* prev_norm, spt_stream_t stream);
+/* The chain's BOTTOM layer K0 -> K folded into the backward of the layer K -> N above it: the bottom
+ * layer is bias-free and its input x0 [rows, K0] (raw f32, no norm in front; 16-byte aligned where
+ * K0 % 4 == 0, else 4-byte) needs
+ * no gradient, so all its backward produces is gW0 [K, K0].  This call takes the sums gW0 is made
+ * of inside the upper layer's kernel, stores no gx and writes gW0 from its post launch (together
+ * with the bottom norm's tables in prev_norm, which is required; W0 [K, K0] = the bottom weight).
+ * _supported: 1 when the shape pair is built for the matrix mode - 12 -> 32 under 32 -> 64 (DMA-staged
+ * backward) and 18 -> 32 under 32 -> 32, in the default f32 mode (f32-exact split forward, split-bf16
+ * backward; no bf16 storage). */
+int spt_fused_linear_bwd_fold_supported(int K0, int K, int N, int mode);
+int spt_fused_linear_bwd_runs_gn_fold_f32(
+    const float* gy, const float* h, int nruns, const int64_t* run_r0, const int64_t* run_r1,
+    const int32_t* run_graph, int num_graphs, int N, const float* am, const float* scale,
+    const float* bias, float slope, const float* c1, const float* c2, const float* c3,
+    const float* xprev, int K, const float* pre_am, const float* pre_scale, const float* pre_bias,
+    float pre_slope, const float* W, float* gW, int mode, void* ws, size_t ws_bytes,
+    const spt_gn_bwd_tables* prev_norm, const float* x0, int K0, const float* W0, float* gW0,
+    spt_stream_t stream);
 int spt_fused_linear_bwd_pooled_runs_gn_f32(
     const float* gout, const int32_t* arg, const int32_t* perm, const int32_t* pos_seg,
     const float* h, int nruns, const int64_t* run_p0, const int64_t* run_p1,

@@ -154,6 +154,10 @@ SIGNATURES = {
     "spt_fused_linear_bwd_runs_gn_f32": (_int, [_p, _p, _int, _p, _p, _p, _int, _int, _p, _p, _p, _f32,
                                                 _p, _p, _p, _p, _int, _p, _p, _p, _f32, _p, _p, _p, _p,
                                                 _int, _p, _sz, _p, _p]),
+    "spt_fused_linear_bwd_fold_supported": (_int, [_int, _int, _int, _int]),
+    "spt_fused_linear_bwd_runs_gn_fold_f32": (_int, [_p, _p, _int, _p, _p, _p, _int, _int, _p, _p, _p, _f32,
+                                                     _p, _p, _p, _p, _int, _p, _p, _p, _f32, _p, _p,
+                                                     _int, _p, _sz, _p, _p, _int, _p, _p, _p]),
     "spt_fused_linear_bwd_pooled_runs_gn_f32": (_int, [_p, _p, _p, _p, _p, _int, _p, _p, _p, _int, _int,
                                                        _p, _p, _p, _f32, _p, _p, _p, _p, _int, _p, _p,
                                                        _p, _f32, _p, _p, _p, _p, _int, _p, _sz, _p, _p]),

@@ -932,8 +932,16 @@ __global__ __launch_bounds__(WAVES_X3 * 64, 2) void fwd_kernel_x3(
 __host__ __device__ constexpr bool fmlp_bf_wg_reduce(int K4, int NBK, int NW) {
   return NBK * 16 <= NW * TR && K4 > 0;          // N rows of the tiles' row stride fit the buffer
 }
+// FK0 > 0 (FOLD): the layer below is the chain's bottom layer FK0 -> K (bias-free, raw input x0
+// without a gradient).  Its weight gradient is made of sums this kernel can take where it holds
+// g' per element (fused_mlp_dma.hip describes the algebra): z = [x0 - s | 1 | 0 ..] padded to ZP
+// columns, A += g'^T z and G += z^T z as 16x16x16 products, one table A [K][ZP] | G [ZP][ZP] per
+// workgroup; gx is not stored.  x0 rows need no alignment beyond their elements' (72-byte rows at
+// K0 = 18: stage_tile's element path).
+constexpr int fold_zp(int K0) { return (K0 + 16) / 16 * 16; }
+constexpr int FOLD_SHIFT_LD = 32;          // row stride of the per-graph shift table
 template <int K4, int NBK, bool NEED_GX, int NW, bool LO, bool POOLED = false, bool PIPE = false,
-          bool H16 = false, bool X16 = false>
+          bool H16 = false, bool X16 = false, int FK0 = 0>
 __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_kernel_bf(
     const float* __restrict__ gy, const float* __restrict__ h, int64_t r0, int64_t r1,
     const float* __restrict__ am, const float* __restrict__ sc, const float* __restrict__ bs,
@@ -943,12 +951,27 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_kernel_bf(
     float pslope, const float* __restrict__ W, float* __restrict__ gx,
     float* __restrict__ gw_partial, double* __restrict__ pstat_partial, FmlpRuns rt,
     const int32_t* __restrict__ perm = nullptr, const int32_t* __restrict__ pos_seg = nullptr,
-    const float* __restrict__ gout = nullptr, const int32_t* __restrict__ arg = nullptr) {
+    const float* __restrict__ gout = nullptr, const int32_t* __restrict__ arg = nullptr,
+    const float* __restrict__ x0 = nullptr, const float* __restrict__ fshift = nullptr,
+    float* __restrict__ fold_partial = nullptr) {
   constexpr int KP = K4 * 4, KB = (KP + 15) / 16, KPP = KB * 16, N = NBK * 16;
   constexpr int NS = (N + 31) / 32, NP32 = NS * 32;
   constexpr int LDG = NP32 + 4, LDX = KPP + 4, LDT = NP32 + 8;
   constexpr bool WGR = fmlp_bf_wg_reduce(K4, NBK, NW);
+  constexpr bool FOLD = FK0 > 0;
+  constexpr int ZP = fold_zp(FOLD ? FK0 : 1), ZB = ZP / 16, LDZ = ZP + 4, FLN = (KPP + ZP) * ZP;
+  static_assert(!FOLD || (WGR && NEED_GX && !POOLED && !PIPE && !H16 && !X16 && KP == KPP && ZP <= 32),
+                "the fold: dense f32 rows, one table per workgroup");
+  static_assert(!FOLD || FLN <= NW * TR * LDX, "the fold table fits the x tile buffers");
   SPT_FMLP_RUN_BWD_T(N, NW, (WGR ? 1 : NW))
+  if constexpr (FOLD) {
+    if (rt.n > 0) {
+      fshift += (size_t)rt.g[blockIdx.y] * FOLD_SHIFT_LD;
+      fold_partial += (size_t)blockIdx.y * gridDim.x * FLN;
+    }
+  }
+  __shared__ __attribute__((aligned(16))) float z_lds[FOLD ? NW : 1][FOLD ? TR * LDZ : 4];  // raw x0 tile
+  __shared__ float fsh[32];                                                                // the graph's shift
   __shared__ __attribute__((aligned(16))) float g_lds[NW][TR * LDG];   // gh tile
   __shared__ __attribute__((aligned(16))) float x_lds[NW][TR * LDX];   // RAW h_prev tile
   __shared__ __attribute__((aligned(16))) __bf16 wt_hi[NEED_GX ? KPP * LDT : 8];
@@ -981,8 +1004,21 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_kernel_bf(
   load_table(pt + 2 * KPP, pbs, K, KPP);
   for (int i = lane; i < TR * LDX; i += 64) xl[i] = 0.f;
   for (int i = lane; i < TR * LDG; i += 64) gl[i] = 0.f;     // columns [N, NP32) stay zero
+  if constexpr (FOLD) {
+    if (threadIdx.x < 32) fsh[threadIdx.x] = (int)threadIdx.x < FK0 ? fshift[threadIdx.x] : 0.f;
+  }
+  float* zl = z_lds[FOLD ? wid : 0];
   __syncthreads();
 
+  // FOLD: FA[kb][zb][r] = A[16 kb + 4 g + r][16 zb + c], FG[za][zb][r] = G[16 za + 4 g + r][16 zb + c]
+  f32x4 FA[FOLD ? KB : 1][ZB], FG[FOLD ? ZB : 1][ZB];
+#pragma unroll
+  for (int zb = 0; zb < ZB; ++zb) {
+#pragma unroll
+    for (int kb = 0; kb < (FOLD ? KB : 1); ++kb) FA[kb][zb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int za = 0; za < (FOLD ? ZB : 1); ++za) FG[za][zb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
   f32x4 C3[NBK][KB];       // C3[nb][kb][r] = gW[16 nb + 4 g + r][16 kb + c]
 #pragma unroll
   for (int nb = 0; nb < NBK; ++nb)
@@ -1145,6 +1181,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_kernel_bf(
       FM_PROBE(0)
       stage_tile<KPP, LDX, KPP, POOLED, (POOLED && NBK >= 8) ? 2 : 4, X16>(xprev, row0, cnt, K, false, pt,
                                                                              pslope, xl, nullptr, lane, rid_l);
+      if constexpr (FOLD)
+        stage_tile<ZP, LDZ, ZP>(x0, row0, cnt, FK0, false, pt, pslope, zl, nullptr, lane);
       FM_PROBE(1)
     }
     const int rid_cur = rid_l;                 // the gx scatter below needs this tile's row ids
@@ -1221,6 +1259,13 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_kernel_bf(
         CX[kb] = mfma3_32<LO>(ah, alo, bfh[step % (LAB + 1)], bfl[step % (LAB + 1)], CX[kb]);
         if constexpr (LAB > 0) __builtin_amdgcn_sched_barrier(0);
       }
+      float ggv[FOLD ? KB : 1][4];
+      if constexpr (FOLD) {
+#pragma unroll
+        for (int kb = 0; kb < KB; ++kb)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) ggv[kb][r] = 0.f;
+      }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int rr = 4 * g + r;
@@ -1231,7 +1276,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_kernel_bf(
             const int k = 16 * kb + c;
             if (k < K) {
               const float v = CX[kb][r];
-              gx[orow * K + k] = v;
+              if constexpr (!FOLD) gx[orow * K + k] = v;
               if (pre) {
                 const float o = xl[rr * LDX + k] - pt[k];
                 float gg = v;
@@ -1241,10 +1286,38 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_kernel_bf(
                 }
                 p1[kb] += (double)gg;
                 p2[kb] += (double)gg * (double)o;
+                if constexpr (FOLD) ggv[kb][r] = gg;
               }
             }
           }
         }
+      }
+      if constexpr (FOLD) {
+        bf16x4 Zh[ZB], Zl[ZB];
+#pragma unroll
+        for (int zb = 0; zb < ZB; ++zb) {
+          const int col = 16 * zb + c;
+          float zv[4];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float raw = zl[(4 * g + r) * LDZ + col];
+            const float in = (col < FK0) ? raw - fsh[col] : ((col == FK0) ? 1.f : 0.f);
+            zv[r] = (4 * g + r < cnt) ? in : 0.f;
+          }
+          split_bf16<4>(zv, Zh[zb], Zl[zb]);
+        }
+#pragma unroll
+        for (int kb = 0; kb < KB; ++kb) {
+          bf16x4 ah, al;
+          split_bf16<4>(ggv[kb], ah, al);
+#pragma unroll
+          for (int zb = 0; zb < ZB; ++zb) FA[kb][zb] = mfma3_16<LO>(ah, al, Zh[zb], Zl[zb], FA[kb][zb]);
+        }
+#pragma unroll
+        for (int za = 0; za < ZB; ++za)
+#pragma unroll
+          for (int zb = 0; zb < ZB; ++zb)
+            FG[za][zb] = mfma3_16<LO>(Zh[za], Zl[za], Zh[zb], Zl[zb], FG[za][zb]);
       }
     }
     FM_PROBE(4)
@@ -1281,6 +1354,48 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void bwd_kernel_bf(
             for (int r = 0; r < 4; ++r) C3[nb][kb][r] += red[(16 * nb + 4 * g + r) * LDX + 16 * kb + c];
       }
       __syncthreads();
+    }
+  }
+  if constexpr (FOLD) {
+    // the fold's sums take the same road (the WGR rounds above end on a barrier)
+    float* red = &x_lds[0][0];
+    for (int w = 1; w < NW; ++w) {
+      if (wid == w) {
+#pragma unroll
+        for (int zb = 0; zb < ZB; ++zb)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+#pragma unroll
+            for (int kb = 0; kb < KB; ++kb) red[(16 * kb + 4 * g + r) * ZP + 16 * zb + c] = FA[kb][zb][r];
+#pragma unroll
+            for (int za = 0; za < ZB; ++za) red[(KPP + 16 * za + 4 * g + r) * ZP + 16 * zb + c] = FG[za][zb][r];
+          }
+      }
+      __syncthreads();
+      if (wid == 0) {
+#pragma unroll
+        for (int zb = 0; zb < ZB; ++zb)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+#pragma unroll
+            for (int kb = 0; kb < KB; ++kb) FA[kb][zb][r] += red[(16 * kb + 4 * g + r) * ZP + 16 * zb + c];
+#pragma unroll
+            for (int za = 0; za < ZB; ++za) FG[za][zb][r] += red[(KPP + 16 * za + 4 * g + r) * ZP + 16 * zb + c];
+          }
+      }
+      __syncthreads();
+    }
+    if (wid == 0) {
+      float* fp = fold_partial + (size_t)blockIdx.x * FLN;
+#pragma unroll
+      for (int zb = 0; zb < ZB; ++zb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+#pragma unroll
+          for (int kb = 0; kb < KB; ++kb) fp[(16 * kb + 4 * g + r) * ZP + 16 * zb + c] = FA[kb][zb][r];
+#pragma unroll
+          for (int za = 0; za < ZB; ++za) fp[(KPP + 16 * za + 4 * g + r) * ZP + 16 * zb + c] = FG[za][zb][r];
+        }
     }
   }
   if (!WGR || wid == 0) {
@@ -1380,8 +1495,9 @@ __global__ __launch_bounds__(1024) void reduce_tables_groups_kernel(const T* __r
 // together - a sum is pure load latency, NV sums one after the other cost NV round-trip chains).
 // Per column the adds happen in reduce_tables_body's order: slices of ceil(ntab / 64) records,
 // then the 64 slice sums in ascending order.  col[v] < 0: column v is not wanted (returns 0).
-template <int NV>
-__device__ __forceinline__ void sliced_col_sums(const double* const (&base)[NV], const int (&ntab)[NV],
+// T: the tables' element type (sums are f64 either way); UNRF > 0 fixes the records in flight.
+template <int NV, typename T = double, int UNRF = 0>
+__device__ __forceinline__ void sliced_col_sums(const T* const (&base)[NV], const int (&ntab)[NV],
                                                 int len, const int (&col)[NV], double (*sl)[17],
                                                 double (&out)[NV]) {
   const int cl = threadIdx.x & 15, slice = threadIdx.x >> 4;
@@ -1400,30 +1516,30 @@ __device__ __forceinline__ void sliced_col_sums(const double* const (&base)[NV],
   // UNR records of every column in flight (12 loads per round trip; one record at a time was
   // 16-32 round trips per slice at a train batch's table counts; more than 12 doubles in flight
   // spill under the 64-register cap of these 1 024-thread blocks)
-  constexpr int UNR = NV <= 3 ? 4 : 1;
+  constexpr int UNR = UNRF > 0 ? UNRF : (NV <= 3 ? 4 : 1);
   int k = 0;
   if constexpr (UNR > 1)
   for (; k + UNR <= kmax; k += UNR) {
-    double t[NV][UNR];
+    T t[NV][UNR];
 #pragma unroll
     for (int j = 0; j < UNR; ++j)
 #pragma unroll
       for (int v = 0; v < NV; ++v)
-        t[v][j] = (lo[v] + k + j < hi[v]) ? base[v][(size_t)(lo[v] + k + j) * len + col[v]] : 0.0;
+        t[v][j] = (lo[v] + k + j < hi[v]) ? base[v][(size_t)(lo[v] + k + j) * len + col[v]] : (T)0;
 #pragma unroll
     for (int j = 0; j < UNR; ++j)
 #pragma unroll
       for (int v = 0; v < NV; ++v)
-        if (lo[v] + k + j < hi[v]) acc[v] += t[v][j];        // (record order: the plain loop's)
+        if (lo[v] + k + j < hi[v]) acc[v] += (double)t[v][j];   // (record order: the plain loop's)
   }
   for (; k < kmax; ++k) {
-    double t[NV];
+    T t[NV];
 #pragma unroll
     for (int v = 0; v < NV; ++v)
-      t[v] = (lo[v] + k < hi[v]) ? base[v][(size_t)(lo[v] + k) * len + col[v]] : 0.0;
+      t[v] = (lo[v] + k < hi[v]) ? base[v][(size_t)(lo[v] + k) * len + col[v]] : (T)0;
 #pragma unroll
     for (int v = 0; v < NV; ++v)
-      if (lo[v] + k < hi[v]) acc[v] += t[v];                 // (record order: the plain loop's)
+      if (lo[v] + k < hi[v]) acc[v] += (double)t[v];         // (record order: the plain loop's)
   }
   // the slices meet through ONE [64][17] buffer, column after column (the loads above were the
   // slow part; a kernel-wide 52 KB of LDS for six buffers halved the residency of the
@@ -1490,14 +1606,127 @@ __global__ __launch_bounds__(1024) void fwd_post_kernel(const double* __restrict
 // channels per block over all graphs (POST_GB of them side by side) with that norm's backward
 // tables written on the spot.
 constexpr int POST_GB = 2;
+// The bottom layer folded into the layer above (FOLD instances of fdma::bwd_dma_kernel and
+// bwd_kernel_bf): per workgroup one table A [K][ZP] | G [ZP][ZP] of f32 sums taken around the
+// per-graph shift s [B][FOLD_SHIFT_LD], ZP = K0 + 1 padded to 16-column blocks; `grp` = the tables of
+// graph b; W0 [K][K0] the bottom layer's weight, am0 [B][K] its norm's am table.  Blocks
+// [first, first + (K / 16) K0) of the post launch: block (cb, k) writes gW0[16 cb .. + 15][k].
+struct FmlpFold {
+  const float* tabs;
+  const float* shift;
+  const float* W0;
+  const float* am0;
+  float* gW0;
+  int K0, ZP, first;
+  FmlpGroups grp;
+};
+// gW0 = sum over graphs of diag(c1) A - diag(c2) Bm - c3 (x) sx, everything below in f64.  With
+// z = x0 - s, d = W0 s - am0 (so that o = W0 z + d):
+//   A  = A_s + (sum g') (x) s                         (sum g' = the statistics' first column)
+//   Bm = o^T x0 = W0 G_s + d (x) sx_s + (sum o) (x) s,   sum o = W0 sx_s + n d
+//   sx = sx_s + n s
+// The coefficients are the f32 values the nB blocks of this launch write for the rest of the
+// backward (re-derived here from the same column sums in the same order: no block waits for
+// another; one record in flight - these blocks have no registers for more).
+__device__ __forceinline__ void bwd_post_fold(const double* __restrict__ pst, const FmlpGroups& grp,
+                                              int K, int B, const spt_gn_bwd_tables& pn,
+                                              const FmlpFold& fd, int bx) {
+  __shared__ double sl[64][17];
+  __shared__ double gk[32], sxs[32];           // G_s[j][k] and sx_s[j] of the graph at hand
+  const int cl = threadIdx.x & 15, slice = threadIdx.x >> 4;
+  const int K0 = fd.K0, ZP = fd.ZP, cb = bx / K0, k = bx - cb * K0;
+  const int c = cb * 16 + cl, len = 2 * K + 1, flen = (K + ZP) * ZP;
+  const bool cv = c < K;
+  double acc = 0.0;
+  for (int b = 0; b < B; ++b) {
+    double s3[3], f3[3], Af = 0.0;
+    const float* ft = fd.tabs + (size_t)fd.grp.start[b] * flen;
+    const float* const fbase[3] = {ft, ft, ft};
+    const int fnt[3] = {fd.grp.count[b], fd.grp.count[b], fd.grp.count[b]};
+#pragma unroll 1
+    for (int jb = 0; jb < ZP / 16; ++jb) {
+      // thread column cl: A[c][k] of its channel (first pass), and row j of the Gram block
+      const int jrow = 16 * jb + cl;
+      const int fcol[3] = {(cv && jb == 0) ? c * ZP + k : -1, (K + jrow) * ZP + k, (K + jrow) * ZP + K0};
+      sliced_col_sums<3, float, 1>(fbase, fnt, flen, fcol, sl, f3);
+      if (slice == 0) {
+        gk[jrow] = f3[1];
+        sxs[jrow] = f3[2];
+      }
+      if (jb == 0) Af = f3[0];
+    }
+    const double* pb = pst + (size_t)grp.start[b] * len;
+    const double* const base[3] = {pb, pb, pb};
+    const int ntab[3] = {grp.count[b], grp.count[b], grp.count[b]};
+    const int col[3] = {cv ? c : -1, cv ? K + c : -1, 2 * K};
+    sliced_col_sums<3, double, 1>(base, ntab, len, col, sl, s3);   // (its barriers publish gk / sxs)
+    if (slice == 0 && cv) {
+      const double w = (double)pn.weight[c], a = (double)pn.mean_scale[c];
+      const double A = s3[0], GO = s3[1], cnt = s3[2];
+      double n = cnt;
+      if (n < 1.0) n = 1.0;
+      const double sd = (double)pn.rstd[b * K + c], mu = (double)pn.mean[b * K + c];
+      const double k2 = w * sd * sd * sd * GO / n;
+      const double sumdo = w * sd * A - k2 * n * mu * (1.0 - a);
+      const double q1 = (double)(float)(w * sd), q2 = (double)(float)k2, q3 = (double)(float)(a * sumdo / n);
+      const double s = (double)fd.shift[b * FOLD_SHIFT_LD + k];
+      double d = -(double)fd.am0[b * K + c], wg = 0.0, ws = 0.0;
+      for (int j = 0; j < K0; ++j) {
+        const double wj = (double)fd.W0[(size_t)c * K0 + j];
+        d += wj * (double)fd.shift[b * FOLD_SHIFT_LD + j];
+        wg += wj * gk[j];
+        ws += wj * sxs[j];
+      }
+      const double so = ws + cnt * d;
+      const double Bm = wg + d * sxs[k] + so * s;
+      acc += q1 * (Af + A * s) - q2 * Bm - q3 * (sxs[k] + cnt * s);
+    }
+    __syncthreads();
+  }
+  if (slice == 0 && cv) fd.gW0[(size_t)c * K0 + k] = (float)acc;
+}
+// the shift of graph b: column means of the first rows (at most 4096) of its first run; thread =
+// (slice of 32, column of 32), eight rows in flight, fixed order
+__global__ __launch_bounds__(1024) void fold_shift_kernel(const float* __restrict__ x0, int K0,
+                                                          FmlpRuns rt, float* __restrict__ shift) {
+  __shared__ float sl[32][33];
+  const int b = blockIdx.x, cl = threadIdx.x & 31, slice = threadIdx.x >> 5;
+  int64_t r0 = 0, r1 = 0;
+  for (int r = rt.n - 1; r >= 0; --r)
+    if (rt.g[r] == b && rt.r1[r] > rt.r0[r]) { r0 = rt.r0[r]; r1 = rt.r1[r]; }
+  if (r1 - r0 > 4096) r1 = r0 + 4096;
+  float acc = 0.f;
+  if (cl < K0) {
+    int64_t i = r0 + slice;
+    for (; i + 7 * 32 < r1; i += 8 * 32) {
+      float t[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) t[u] = x0[(i + 32 * u) * K0 + cl];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) acc += t[u];
+    }
+    for (; i < r1; i += 32) acc += x0[i * K0 + cl];
+  }
+  sl[slice][cl] = acc;
+  __syncthreads();
+  if (slice == 0) {
+    double t = 0;
+    for (int k = 0; k < 32; ++k) t += (double)sl[k][cl];
+    shift[b * FOLD_SHIFT_LD + cl] = (cl < K0 && r1 > r0) ? (float)(t / (double)(r1 - r0)) : 0.f;
+  }
+}
 __global__ __launch_bounds__(1024, 8) void bwd_post_kernel(const float* __restrict__ gwp, int ntab_w,
                                                         int NK, float* __restrict__ gW, int accumulate,
                                                         int nA, const double* __restrict__ pst,
                                                         FmlpGroups grp, int K, int B,
                                                         double* __restrict__ prev_total,
-                                                        spt_gn_bwd_tables pn) {
+                                                        spt_gn_bwd_tables pn, FmlpFold fd) {
   if ((int)blockIdx.x < nA) {
     reduce_tables_body<float>(gwp, ntab_w, NK, gW, accumulate, (int)blockIdx.x);
+    return;
+  }
+  if (fd.tabs && (int)blockIdx.x >= fd.first) {
+    bwd_post_fold(pst, grp, K, B, pn, fd, (int)blockIdx.x - fd.first);
     return;
   }
   const int bx = (int)blockIdx.x - nA, len = 2 * K + 1;
@@ -1567,14 +1796,22 @@ __global__ __launch_bounds__(1024, 8) void bwd_post_kernel(const float* __restri
 
 static void bwd_post_launch(const float* gwp, int ntab_w, int NK, float* gW, int accumulate,
                             const double* pst, const FmlpGroups& grp, int K, int B,
-                            double* prev_total, const spt_gn_bwd_tables* pn, hipStream_t stream) {
+                            double* prev_total, const spt_gn_bwd_tables* pn, hipStream_t stream,
+                            const FmlpFold* fold = nullptr) {
   const int nA = (NK + 15) / 16;
   spt_gn_bwd_tables none = {};
   int nB = 0;
   if (pn && pn->c1) nB = (K + 15) / 16;
   else if (prev_total) nB = ((2 * K + 1 + 15) / 16) * B;
-  bwd_post_kernel<<<nA + nB, 1024, 0, stream>>>(gwp, ntab_w, NK, gW, accumulate, nA, pst, grp, K, B,
-                                                prev_total, (pn && pn->c1) ? *pn : none);
+  FmlpFold fd = {};
+  int nF = 0;
+  if (fold) {                                  // (needs pn: the bottom norm's coefficients)
+    fd = *fold;
+    fd.first = nA + nB;
+    nF = ((K + 15) / 16) * fd.K0;
+  }
+  bwd_post_kernel<<<nA + nB + nF, 1024, 0, stream>>>(gwp, ntab_w, NK, gW, accumulate, nA, pst, grp, K, B,
+                                                     prev_total, (pn && pn->c1) ? *pn : none, fd);
 }
 
 static int grid_for_nw(int64_t rows, int per_cu, int nwv) {
@@ -1606,7 +1843,11 @@ int fmlp_dma_bwd_launch(bool pooled, bool lo, const float* gy, const float* h, F
                         const float* pbs, float pslope, const float* W, float* gx,
                         float* gw_partial, double* pstat_partial, const int32_t* perm,
                         const int32_t* pos_seg, const float* gout, const int32_t* arg,
-                        hipStream_t stream, bool s16 = false, int* gw_tabs = nullptr);
+                        hipStream_t stream, bool s16 = false, int* gw_tabs = nullptr,
+                        const float* x0 = nullptr, const float* fshift = nullptr,
+                        float* fold_partial = nullptr, int K0 = 0);
+bool fmlp_dma_fold_supported(int K0, int K, int N);
+int fmlp_fold_len(int K, int K0);
 }  // namespace spt
 
 using namespace spt;
@@ -1878,9 +2119,18 @@ static int fmlp_bwd_impl(bool pooled, const float* gy, const float* gout, const 
                          int K, const float* pre_am, const float* pre_scale, const float* pre_bias,
                          float pre_slope, const float* W, float* gx, float* gW, int accumulate,
                          double* prev_total, int mode, void* ws, size_t ws_bytes,
-                         hipStream_t stream, const spt_gn_bwd_tables* prev_norm = nullptr) {
+                         hipStream_t stream, const spt_gn_bwd_tables* prev_norm = nullptr,
+                         const float* fold_x0 = nullptr, int fold_K0 = 0, const float* fold_W0 = nullptr,
+                         float* fold_gW0 = nullptr) {
   const int g_fmlp_mode = fmlp_mode_of(mode);
   const bool g_fmlp_split_bf16 = g_fmlp_mode >= 1;
+  if (fold_x0) {
+    // the bottom layer K0 -> K folded into this one: no gx, gW0 out of the post launch
+    SPT_CHECK_ARG(!pooled && !gx && fold_W0 && fold_gW0 && prev_norm && pre_am,
+                  "fold: dense layer, no gx, norm tables");
+    SPT_CHECK_ARG(spt_fused_linear_bwd_fold_supported(fold_K0, K, N, mode), "fold: shape pair or mode not built");
+    SPT_CHECK_ARG(((size_t)fold_x0 & (fold_K0 % 4 == 0 ? 15 : 3)) == 0, "fold: x0 alignment");
+  }
   // (prev_norm: the previous layer's backward tables are written by this call's post launch; its
   // statistics are then needed whether or not the caller wants the totals themselves)
   const bool want_prev = prev_total || prev_norm;
@@ -1899,7 +2149,7 @@ static int fmlp_bwd_impl(bool pooled, const float* gy, const float* gout, const 
   } else {
     SPT_CHECK_ARG(spt_fused_linear_supported(K, N), "(K, N) not built");
     SPT_CHECK_ARG(gy, "null pointer");
-    SPT_CHECK_ARG(!want_prev || (gx && pre_am), "previous-layer statistics need gx and its tables");
+    SPT_CHECK_ARG(!want_prev || ((gx || fold_x0) && pre_am), "previous-layer statistics need gx and its tables");
   }
   const int k4 = (K + 3) / 4, nbk = N / 16;
   int gx_ = 1, nwv = 1;                        // blocks per run, waves per block
@@ -1985,6 +2235,8 @@ static int fmlp_bwd_impl(bool pooled, const float* gy, const float* gout, const 
           gy, h, 0, 0, am, scale, bias, slope, c1, c2, c3, xprev, K, pre_am, pre_scale,          \
           pre_bias, pre_slope, W, nullptr, gwp, nullptr, rt);                                    \
   }
+  float* fold_tabs = nullptr;
+  float* fold_shift = nullptr;
   int per_run = 0;                              // wave records per run (statistics tables)
   int gw_tabs = 0;                              // weight-gradient tables per run (one per wave, or
                                                 // one per workgroup: fmlp_bf_wg_reduce)
@@ -2047,6 +2299,35 @@ static int fmlp_bwd_impl(bool pooled, const float* gy, const float* gout, const 
     }
 #undef XSP
 #undef XSD
+  } else if (fold_x0) {
+    // fold tables and the shift live in the tail of the weight-gradient table region: every fold
+    // instance writes one table per workgroup, at most FOLD_MAX_TABS over all runs (checked below)
+    constexpr size_t FOLD_MAX_TABS = 1024;
+    const int flen = fmlp_fold_len(K, fold_K0);
+    SPT_CHECK_ARG((FOLD_MAX_TABS * ((size_t)N * K + flen) + FMLP_MAX_RUNS * FOLD_SHIFT_LD) * 4 <=
+                  (size_t)MAX_BWD_WAVES * N * K * 4, "fold: tables do not fit the workspace");
+    fold_tabs = gwp + FOLD_MAX_TABS * N * K;
+    fold_shift = fold_tabs + FOLD_MAX_TABS * flen;
+    fold_shift_kernel<<<num_graphs, 1024, 0, stream>>>(fold_x0, fold_K0, rt, fold_shift);
+    if (fmlp_dma_of(mode) && fmlp_dma_fold_supported(fold_K0, K, N)) {
+      per_run = fmlp_dma_bwd_launch(false, true, gy, h, rt, max_rows, N, am, scale, bias, slope, c1, c2,
+                                    c3, xprev, K, pre_am, pre_scale, pre_bias, pre_slope, W, nullptr,
+                                    gwp, pstp, nullptr, nullptr, nullptr, nullptr, stream, false,
+                                    &gw_tabs, fold_x0, fold_shift, fold_tabs, fold_K0);
+    } else if (fold_K0 == 18 && k4 == 8 && nbk == 2) {
+      // the edge MLP's 18 -> 32 under 32 -> 32: the grid of the plain <8, 2> launch
+      constexpr int NWB = 4;
+      gx_ = cap_grid(grid_for_nw(max_rows, 4, NWB), NWB);
+      nwv = NWB;
+      gw_tabs = gx_;
+      const dim3 grid((unsigned)gx_, (unsigned)nr);
+      bwd_kernel_bf<8, 2, true, NWB, true, false, false, false, false, 18><<<grid, NWB * 64, 0, stream>>>(
+          gy, h, 0, 0, am, scale, bias, slope, c1, c2, c3, xprev, K, pre_am, pre_scale, pre_bias,
+          pre_slope, W, nullptr, gwp, pstp, rt, nullptr, nullptr, nullptr, nullptr, fold_x0, fold_shift,
+          fold_tabs);
+      per_run = gx_ * nwv;
+    }
+    SPT_CHECK_ARG((size_t)gw_tabs * nr <= FOLD_MAX_TABS, "fold: more tables than the workspace layout holds");
   } else if (g_fmlp_split_bf16 && gx && fmlp_dma_of(mode) && fmlp_dma_supported(K, N)) {
     per_run = fmlp_dma_bwd_launch(pooled, g_fmlp_mode != 3, gy, h, rt, max_rows, N, am, scale, bias,
                                   slope, c1, c2, c3, xprev, K, pre_am, pre_scale, pre_bias, pre_slope,
@@ -2064,8 +2345,19 @@ static int fmlp_bwd_impl(bool pooled, const float* gy, const float* gout, const 
   // ONE post launch: the weight gradient's sum, the previous layer's statistics and - prev_norm -
   // that layer's backward tables (they were three launches: two here, gn_bwd_tables_kernel behind
   // a second C entry)
+  FmlpFold fd = {};
+  if (fold_x0) {
+    fd.tabs = fold_tabs;
+    fd.shift = fold_shift;
+    fd.gW0 = fold_gW0;
+    fd.W0 = fold_W0;
+    fd.am0 = pre_am;
+    fd.K0 = fold_K0;
+    fd.ZP = fold_zp(fold_K0);
+    fd.grp = fmlp_groups(rt, num_graphs, gw_tabs);
+  }
   bwd_post_launch(gwp, gw_tabs * nr, N * K, gW, accumulate, pst, fmlp_groups(rt, num_graphs, per_run), K,
-                  num_graphs, prev_total, prev_norm, stream);
+                  num_graphs, prev_total, prev_norm, stream, fold_x0 ? &fd : nullptr);
   SPT_CHECK_LAUNCH();
   return 0;
 }
@@ -2205,6 +2497,38 @@ extern "C" int spt_fused_linear_bwd_runs_gn_f32(
                        am, scale, bias, slope, c1, c2, c3, xprev, K, pre_am, pre_scale, pre_bias,
                        pre_slope, W, gx, gW, 0, prev_total, mode, ws, ws_bytes, (hipStream_t)stream_,
                        prev_norm);
+}
+
+// The bottom layer of a chain folded into the layer above it.  The bottom layer
+// K0 -> K is bias-free and its input x0 [rows, K0] (raw, 16-byte aligned, no norm in front) needs
+// no gradient, so its backward only forms gW0 = gh0^T x0; this call - the backward of K -> N above
+// it - takes the sums gW0 is made of next to the statistics of the bottom norm's backward, stores
+// no gx and writes gW0 [K, K0] from its post launch.  Arguments as spt_fused_linear_bwd_runs_gn_f32
+// without gx; prev_norm (required) describes the bottom layer's norm, W0 [K, K0] is its weight.
+extern "C" int spt_fused_linear_bwd_fold_supported(int K0, int K, int N, int mode) {
+  const int m = fmlp_mode_of(mode);
+  if (mode >= 0 && (mode & (SPT_FMLP_H_BF16 | SPT_FMLP_X_BF16))) return 0;
+  // (the Gram stands in for o^T x0: the forward must have formed h0 = W0 x0 to f32 accuracy)
+  return m == 1 && g_fmlp_x3 &&
+         ((fmlp_dma_of(mode) && fmlp_dma_fold_supported(K0, K, N)) || (K0 == 18 && K == 32 && N == 32));
+}
+extern "C" int spt_fused_linear_bwd_runs_gn_fold_f32(
+    const float* gy, const float* h, int nruns, const int64_t* run_r0, const int64_t* run_r1,
+    const int32_t* run_graph, int num_graphs, int N, const float* am, const float* scale,
+    const float* bias, float slope, const float* c1, const float* c2, const float* c3,
+    const float* xprev, int K, const float* pre_am, const float* pre_scale, const float* pre_bias,
+    float pre_slope, const float* W, float* gW, int mode, void* ws, size_t ws_bytes,
+    const spt_gn_bwd_tables* prev_norm, const float* x0, int K0, const float* W0, float* gW0,
+    spt_stream_t stream_) {
+  FmlpRuns rt;
+  int64_t max_rows;
+  const char* err = fmlp_make_runs(nruns, run_r0, run_r1, run_graph, num_graphs, &rt, &max_rows);
+  SPT_CHECK_ARG(!err, err ? err : "");
+  SPT_CHECK_ARG(prev_norm && x0 && W0 && gW0, "null pointer");
+  return fmlp_bwd_impl(false, gy, nullptr, nullptr, nullptr, nullptr, h, rt, max_rows, num_graphs, N,
+                       am, scale, bias, slope, c1, c2, c3, xprev, K, pre_am, pre_scale, pre_bias,
+                       pre_slope, W, nullptr, gW, 0, nullptr, mode, ws, ws_bytes, (hipStream_t)stream_,
+                       prev_norm, x0, K0, W0, gW0);
 }
 
 // ---- the top layer fused with the max-pool behind it (fused_pool.hip) -----------------------------

@@ -125,7 +125,22 @@ __device__ __forceinline__ int pick_lane(int v, int base, int sel) {
 // visited in ascending order, so an f32 block never overwrites bf16 rows that are still to be read
 // (block i ends at byte 1024 (i + 1) <= the first unread bf16 row).  Everything downstream (the two
 // GEMMs, the statistics, gx as f32 rows) is unchanged.
-template <int K, int N, int NW, int OCC, bool LO, bool POOLED, bool S16 = false>
+// FOLD (dense f32 rows only): the layer BELOW is the chain's bottom layer - bias-free, its input
+// x0 [rows, FOLD_K0] raw and without a gradient - so gx (= that layer's g1) has one reader, the
+// pass that forms gW0 = gh0^T x0 with gh0 = c1 g' - c2 o - c3.  The coefficients are known only
+// after this launch, but g' and o exist per element in the statistics block below, so the three
+// sums gW0 is made of are taken here instead:
+//   A = g'^T z,  G = z^T z,  z = [x0 - s | 1 | 0 0 0]      (s: a per-graph shift)
+// as 16x16x16 products in the layout of the gW product (one per k block for A, one for G).  G
+// stands in for Bm = o^T (x0 - s): the bottom layer has no bias and no norm in front, o = W0 x0 - am,
+// so Bm = W0 G' - am (x) sx with G' the Gram block and sx = column FOLD_K0 of G (the ones column;
+// G[FOLD_K0][FOLD_K0] = the row count).  gx is not stored; the post launch (fused_mlp.hip) undoes
+// the shift in f64 and writes gW0.  One table of fold_len(K, FK0) floats per workgroup: A [K][16] | G [16][16].
+// (the table layout - A [K][ZP] | G [ZP][ZP], ZP = K0 + 1 padded to whole 16-column blocks - is
+// shared with fused_mlp.hip's register-staged FOLD instance and its post launch)
+constexpr int fold_len(int K, int K0) { return (K + (K0 + 16) / 16 * 16) * ((K0 + 16) / 16 * 16); }
+// FK0 = K0 of the folded bottom layer (0: no fold); rows of whole 16-byte chunks, one 1 KB block per tile
+template <int K, int N, int NW, int OCC, bool LO, bool POOLED, bool S16 = false, int FK0 = 0>
 __global__ __launch_bounds__(NW * 64, OCC) void bwd_dma_kernel(
     const float* __restrict__ gy, const float* __restrict__ h, int64_t r0, int64_t r1,
     const float* __restrict__ am, const float* __restrict__ sc, const float* __restrict__ bs,
@@ -135,7 +150,13 @@ __global__ __launch_bounds__(NW * 64, OCC) void bwd_dma_kernel(
     float pslope, const float* __restrict__ W, float* __restrict__ gx,
     float* __restrict__ gw_partial, double* __restrict__ pstat_partial,
     const int32_t* __restrict__ perm, const int32_t* __restrict__ pos_seg,
-    const float* __restrict__ gout, const int32_t* __restrict__ arg, FmlpRuns rt) {
+    const float* __restrict__ gout, const int32_t* __restrict__ arg, FmlpRuns rt,
+    const float* __restrict__ x0 = nullptr, const float* __restrict__ fshift = nullptr,
+    float* __restrict__ fold_partial = nullptr) {
+  constexpr bool FOLD = FK0 > 0;
+  constexpr int FOLD_K0 = FK0;
+  static_assert(!FOLD || (!POOLED && !S16), "the fold reads dense f32 rows");
+  static_assert(!FOLD || (FK0 % 4 == 0 && FK0 < 16 && TR * FK0 * 4 <= 1024), "x0 tile: one DMA block, one k block");
   constexpr int NC = N / 4, KC = K / 4, NBK = N / 16, KB = K / 16, NS = N / 32;
   if (rt.n > 0) {                           // multi-run launch (common.hpp): blockIdx.y = run
     const int run_ = blockIdx.y, gph_ = rt.g[run_];
@@ -146,6 +167,10 @@ __global__ __launch_bounds__(NW * 64, OCC) void bwd_dma_kernel(
     if (pam) { pam += (size_t)gph_ * K; psc += (size_t)gph_ * K; }
     gw_partial += (size_t)run_ * gridDim.x * N * K;          // one table per workgroup (epilogue)
     if (pstat_partial) pstat_partial += (size_t)run_ * gridDim.x * NW * (2 * K + 1);
+    if constexpr (FOLD) {
+      fshift += (size_t)gph_ * 32;
+      fold_partial += (size_t)run_ * gridDim.x * fold_len(K, FK0);
+    }
   }
   constexpr int HI = TR * NC / 64, XI = TR * KC / 64;   // DMA instructions per tile (h, x)
   constexpr int RH = 64 / NC;                            // rows of h per DMA instruction
@@ -157,6 +182,9 @@ __global__ __launch_bounds__(NW * 64, OCC) void bwd_dma_kernel(
   __shared__ __attribute__((aligned(16))) __bf16 wt_hi[K * LDT];
   __shared__ __attribute__((aligned(16))) __bf16 wt_lo[LO ? K * LDT : 8];
   __shared__ __attribute__((aligned(16))) float pt[3 * K];      // previous norm: am | sc | bs
+  // FOLD: the tile's 16 rows of x0 are one contiguous 768-byte block: ONE DMA instruction (1 KB)
+  __shared__ __attribute__((aligned(16))) float x0b[FOLD ? NW : 1][FOLD ? 256 : 4];
+  __shared__ float fsh[16];                                     // FOLD: the graph's shift
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int g = lane >> 4, c = lane & 15;
@@ -171,6 +199,9 @@ __global__ __launch_bounds__(NW * 64, OCC) void bwd_dma_kernel(
     const __bf16 hh = (__bf16)w;
     wt_hi[k * LDT + n] = hh;
     if constexpr (LO) wt_lo[k * LDT + n] = (__bf16)(w - (float)hh);
+  }
+  if constexpr (FOLD) {
+    if (threadIdx.x < 16) fsh[threadIdx.x] = threadIdx.x < FOLD_K0 ? fshift[threadIdx.x] : 0.f;
   }
   for (int i = threadIdx.x; i < K; i += NW * 64) {
     pt[i] = pre ? pam[i] : 0.f;
@@ -187,6 +218,11 @@ __global__ __launch_bounds__(NW * 64, OCC) void bwd_dma_kernel(
   double p1[KB], p2[KB];
 #pragma unroll
   for (int kb = 0; kb < KB; ++kb) p1[kb] = p2[kb] = 0.0;
+  // FOLD: FA[kb][r] = A[16 kb + 4 g + r][c], FG[r] = G[4 g + r][c]
+  f32x4 FA[FOLD ? KB : 1], FG = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int kb = 0; kb < (FOLD ? KB : 1); ++kb) FA[kb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  float* X0B = x0b[FOLD ? wid : 0];
 
   const int64_t ntiles = (r1 - r0 + TR - 1) / TR;
   const int64_t wave = (int64_t)blockIdx.x * NW + wid;
@@ -286,6 +322,13 @@ __global__ __launch_bounds__(NW * 64, OCC) void bwd_dma_kernel(
   auto issue_x = [&](int64_t t, int rid_l) {
     if (t >= ntiles) return;
     const int64_t row0 = r0 + t * TR;
+    if constexpr (FOLD) {
+      // lane L < 48: floats [4 L, 4 L + 4) of the tile's block; the other lanes, and a short last
+      // tile's lanes past its rows, re-read the block's last whole chunk (never past row r1 - 1)
+      const int cnt = (int)((r1 - row0) < TR ? (r1 - row0) : TR);
+      const int last = cnt * FOLD_K0 - 4;
+      lds_dma16(x0 + row0 * FOLD_K0 + (4 * ln < last ? 4 * ln : last), X0B);
+    }
     if constexpr (S16) {
       const uint16_t* xb = reinterpret_cast<const uint16_t*>(xprev) + (POOLED ? 0 : row0 * K);
       const int x16 = ln / KC16, q16 = ln % KC16;
@@ -446,9 +489,23 @@ __global__ __launch_bounds__(NW * 64, OCC) void bwd_dma_kernel(
     // (f64 per element, like the register-staged kernel: sum g' and sum g' o' cancel to a small
     //  fraction of their terms - f32 partial sums over the 4 rows of a lane moved the input
     //  gradient three layers down by more than 1e-5 of its entries)
+    bf16x4 X0h, X0l;                                 // FOLD: [x0 - s | 1 | 0 0 0] of this lane's rows
+    if constexpr (FOLD) {
+      float x0v[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int rr = 4 * g + r;
+        const float xr = X0B[rr * FOLD_K0 + (c < FOLD_K0 ? c : 0)];
+        const float one = (c == FOLD_K0) ? 1.f : 0.f;
+        x0v[r] = (rr < cnt) ? ((c < FOLD_K0) ? xr - fsh[c] : one) : 0.f;
+      }
+      split_bf16<4>(x0v, X0h, X0l);
+      FG = mfma3_16<LO>(X0h, X0l, X0h, X0l, FG);
+    }
 #pragma unroll
     for (int kb = 0; kb < KB; ++kb) {
       const int k = 16 * kb + c;
+      float ggv[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float* xs = XB + (4 * g + r) * K + 4 * ((4 * kb + (c >> 2)) ^ (4 * (g & 1))) + (c & 3);
@@ -462,18 +519,26 @@ __global__ __launch_bounds__(NW * 64, OCC) void bwd_dma_kernel(
           }
           p1[kb] += (double)gg;
           p2[kb] += (double)gg * (double)o;
+          if constexpr (FOLD) ggv[r] = gg;
         }
-        *xs = v;
+        if constexpr (!FOLD) *xs = v;
+      }
+      if constexpr (FOLD) {
+        bf16x4 ah, al;
+        split_bf16<4>(ggv, ah, al);
+        FA[kb] = mfma3_16<LO>(ah, al, X0h, X0l, FA[kb]);
       }
     }
-    lds_order();
+    if constexpr (!FOLD) {
+      lds_order();
 #pragma unroll
-    for (int i = 0; i < XI; ++i) {
-      const int rr = hx + RX * i;
-      const float4 v = *reinterpret_cast<const float4*>(XB + rr * K + 4 * px);
-      const int64_t orow = POOLED ? (int64_t)pickx(rid_cur, RX * i) : row0 + rr;
-      if (!(SPT_FDMA_SKIP & 16) && rr < cnt)
-        *reinterpret_cast<float4*>(gx + orow * K + 4 * (px ^ (4 * ((rr >> 2) & 1)))) = v;
+      for (int i = 0; i < XI; ++i) {
+        const int rr = hx + RX * i;
+        const float4 v = *reinterpret_cast<const float4*>(XB + rr * K + 4 * px);
+        const int64_t orow = POOLED ? (int64_t)pickx(rid_cur, RX * i) : row0 + rr;
+        if (!(SPT_FDMA_SKIP & 16) && rr < cnt)
+          *reinterpret_cast<float4*>(gx + orow * K + 4 * (px ^ (4 * ((rr >> 2) & 1)))) = v;
+      }
     }
     wait_lds();
     issue_x(t + nwaves, rid_n);
@@ -521,6 +586,41 @@ __global__ __launch_bounds__(NW * 64, OCC) void bwd_dma_kernel(
         for (int r = 0; r < 4; ++r)
           gwp[(size_t)(16 * nb + 4 * g + r) * K + 16 * kb + c] = C3[nb][kb][r];
   }
+  if constexpr (FOLD) {
+    // the fold's sums take the same road: waves 1 .. NW - 1 hand theirs to wave 0 in turn
+    constexpr int FLN = fold_len(K, FK0);
+    static_assert(FLN <= NW * (W_H + W_X + 2 * W_G), "the fold table fits the tile buffers");
+    float* red = &lw[0][0];
+    for (int w = 1; w < NW; ++w) {
+      if (wid == w) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+#pragma unroll
+          for (int kb = 0; kb < KB; ++kb) red[(16 * kb + 4 * g + r) * 16 + c] = FA[kb][r];
+          red[(K + 4 * g + r) * 16 + c] = FG[r];
+        }
+      }
+      __syncthreads();
+      if (wid == 0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+#pragma unroll
+          for (int kb = 0; kb < KB; ++kb) FA[kb][r] += red[(16 * kb + 4 * g + r) * 16 + c];
+          FG[r] += red[(K + 4 * g + r) * 16 + c];
+        }
+      }
+      __syncthreads();
+    }
+    if (wid == 0) {
+      float* fp = fold_partial + (size_t)blockIdx.x * FLN;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+#pragma unroll
+        for (int kb = 0; kb < KB; ++kb) fp[(16 * kb + 4 * g + r) * 16 + c] = FA[kb][r];
+        fp[(K + 4 * g + r) * 16 + c] = FG[r];
+      }
+    }
+  }
   if (pstat_partial) {
     double* pp = pstat_partial + (size_t)wave * (2 * K + 1);
 #pragma unroll
@@ -538,10 +638,16 @@ __global__ __launch_bounds__(NW * 64, OCC) void bwd_dma_kernel(
 }  // namespace fdma
 
 // (K, N) with a DMA-staged backward: the point MLP's 64 -> 128, 32 -> 64 and (panoptic) 64 -> 64
+// (K0, K, N) of a bottom layer K0 -> K folded into the DMA-staged backward of K -> N above it
+bool fmlp_dma_fold_supported(int K0, int K, int N) {
+  return K0 == 12 && K == 32 && N == 64;
+}
+int fmlp_fold_len(int K, int K0) { return fdma::fold_len(K, K0); }
 bool fmlp_dma_supported(int K, int N) {
   return (K == 64 && N == 128) || (K == 32 && N == 64) || (K == 64 && N == 64);
 }
 
+bool fmlp_dma_fold_supported(int K0, int K, int N);
 // Launches the layer's backward; returns the number of per-wave partial tables written
 // (gw_partial: [workgroups][N x K], pstat_partial: [waves][2 K + 1] or null), 0 if (K, N) is not built.
 // returns the number of wave records PER RUN written to the statistics tables (0: shape not built);
@@ -553,10 +659,24 @@ int fmlp_dma_bwd_launch(bool pooled, bool lo, const float* gy, const float* h, F
                         const float* pbs, float pslope, const float* W, float* gx,
                         float* gw_partial, double* pstat_partial, const int32_t* perm,
                         const int32_t* pos_seg, const float* gout, const int32_t* arg,
-                        hipStream_t stream, bool s16, int* gw_tabs) {
+                        hipStream_t stream, bool s16, int* gw_tabs, const float* x0,
+                        const float* fshift, float* fold_partial, int K0) {
   using namespace fdma;
   const int64_t tiles = (max_rows + TR - 1) / TR;
   const int nr = rt.n < 1 ? 1 : rt.n;
+  if (x0) {                                 // FOLD: the 12 -> 32 layer under 32 -> 64 (same grid)
+    if (!fmlp_dma_fold_supported(K0, K, N) || pooled || s16 || !lo || !fshift || !fold_partial || !pam) return 0;
+    int64_t blocks = (tiles + 8 - 1) / 8;
+    const int64_t cap = (256 * 2) / nr > 1 ? (256 * 2) / nr : 1;
+    if (blocks > cap) blocks = cap;
+    if (blocks < 1) blocks = 1;
+    const dim3 grid((unsigned)blocks, (unsigned)nr);
+    bwd_dma_kernel<32, 64, 8, 4, true, false, false, 12><<<grid, 8 * 64, 0, stream>>>(
+        gy, h, 0, 0, am, sc, bs, slope, c1, c2, c3, xprev, pam, psc, pbs, pslope, W, nullptr,
+        gw_partial, pstat_partial, perm, pos_seg, gout, arg, rt, x0, fshift, fold_partial);
+    if (gw_tabs) *gw_tabs = (int)blocks;
+    return (int)blocks * 8;
+  }
 #define SPT_DMA_CASE(KK, NN, NWV, PER_CU, OCC)                                                        \
   if (K == KK && N == NN) {                                                                        \
     int64_t blocks = (tiles + NWV - 1) / NWV;                                                      \

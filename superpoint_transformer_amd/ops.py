@@ -1736,6 +1736,22 @@ def fuse_post(on=None):
     return old
 
 
+# The chain's bottom layer folded into the backward of the layer above it: where the
+# chain's input needs no gradient, the bottom layer's backward only forms gW0 - from sums the upper
+# layer's kernel can take while it holds g' and the tile (spt_fused_linear_bwd_runs_gn_fold_f32): no
+# [rows, K] gradient is written or read, no bottom-layer launch.  Default on; SPT_FMLP_FOLD_BOTTOM=0
+# or fold_bottom(False) select the layer-by-layer route (A/B, tests).
+FOLD_BOTTOM = os.environ.get("SPT_FMLP_FOLD_BOTTOM", "1") != "0"
+
+
+def fold_bottom(on=None):
+    global FOLD_BOTTOM
+    old = FOLD_BOTTOM
+    if on is not None:
+        FOLD_BOTTOM = bool(on)
+    return old
+
+
 def _fmlp_backward(saved, meta, gy, top_total=None, pooled=None, top_tabs=None):
     """Backward of the fused layer chain from the gradient of its (normalised) output.
     ``top_total``: statistics of the top GraphNorm's backward when the caller already has
@@ -1792,7 +1808,14 @@ def _fmlp_backward(saved, meta, gy, top_total=None, pooled=None, top_tabs=None):
                 _lib.check(st, "spt_graphnorm_bwd_tables_f32")
             xprev = hs[l - 1] if l else x2
             pre = tabs[l - 1] if l else None
-            want_gx = l > 0 or need_gx0
+            lmode = (3 | _ST_H | (_ST_X if l else 0)) if store16 else fmode
+            # the bottom layer rides along (see FOLD_BOTTOM): this layer's gx is then never formed
+            fold = (l == 1 and FOLD_BOTTOM and FUSE_POST and not need_gx0 and not store16
+                    and not (pooled is not None and l == L - 1)
+                    and x2.dtype == torch.float32 and x2.data_ptr() % 16 == 0
+                    and bool(_lib.lib.spt_fused_linear_bwd_fold_supported(
+                        int(Ws[0].shape[1]), K, N, lmode)))
+            want_gx = (l > 0 or need_gx0) and not fold
             gx = torch.empty((R, K), dtype=torch.float32, device=dev) if want_gx else None
             gW = torch.empty((N, K), dtype=torch.float32, device=dev)
             # the previous layer's backward tables: written by THIS call's post launch (FUSE_POST),
@@ -1809,7 +1832,21 @@ def _fmlp_backward(saved, meta, gy, top_total=None, pooled=None, top_tabs=None):
             pa = ps = pb = None
             if pre is not None:
                 pa, ps, pb = pre[2], pre[3], gnb[l - 1]
-            lmode = (3 | _ST_H | (_ST_X if l else 0)) if store16 else fmode
+            if fold:
+                K0 = int(Ws[0].shape[1])
+                gW0 = torch.empty((K, K0), dtype=torch.float32, device=dev)
+                with _timed(f"fused_linear_bwd_fold:{K0}x{K}x{N}:{R}"):
+                    st = _lib.lib.spt_fused_linear_bwd_runs_gn_fold_f32(
+                        _lib.ptr(g_cur), _lib.ptr(hs[l]), nr, c_r0, c_r1, c_g, B, N,
+                        _lib.ptr(am), _lib.ptr(sc), _lib.ptr(gnb[l]), float(slopes[l]),
+                        _lib.ptr(c1), _lib.ptr(c2), _lib.ptr(c3), _lib.ptr(xprev), K,
+                        _lib.ptr(pa), _lib.ptr(ps), _lib.ptr(pb), float(slopes[0]), _lib.ptr(Ws[l]),
+                        _lib.ptr(gW), lmode, _lib.ptr(ws), ws.numel(), ctypes.addressof(pn),
+                        _lib.ptr(x2), K0, _lib.ptr(Ws[0]), _lib.ptr(gW0), sp)
+                _lib.check(st, "spt_fused_linear_bwd_runs_gn_fold_f32")
+                grads[4], grads[5], grads[6], grads[7] = gW, gw_n, gb_n, ga_n
+                grads[0], grads[1], grads[2], grads[3] = gW0, nxt_tabs[3], nxt_tabs[4], nxt_tabs[5]
+                break
             if pooled is not None and l == L - 1:
                 p_gout, p_arg, p_csr = pooled
                 args = (_lib.ptr(p_gout), _lib.ptr(p_arg), _lib.ptr(p_csr.perm),
