@@ -443,7 +443,7 @@ extern "C" int spt_adjacency_regression(const int64_t* neighbors, const float* d
 
 extern "C" size_t spt_adjacency_count_workspace_bytes(int64_t num_nodes) {
   if (num_nodes < 0) return 0;
-  return align_up((size_t)ceil_div(num_nodes + 1, SCAN_TILE) * 4, 256);
+  return scan_part_bytes(num_nodes + 1);
 }
 
 extern "C" int spt_adjacency_count(const int64_t* neighbors, int64_t num_nodes, int64_t ld, int k,
@@ -468,7 +468,9 @@ extern "C" int spt_adjacency_count(const int64_t* neighbors, int64_t num_nodes, 
            k_isolated};
     count_kernel<<<stream_grid(t.n + t.n_iso, THREADS), THREADS, 0, stream>>>(t, keep, row_start);
   }
-  device_exclusive_scan(row_start, n + 1, (uint32_t*)ws, stream);
+  SPT_CHECK_ARG(device_exclusive_scan(row_start, n + 1, (uint32_t*)ws,
+                                      (int64_t)(ws_bytes / 4), stream) == 0,
+                "scan partials do not fit their region");
   SPT_CHECK_LAUNCH();
   return 0;
 }

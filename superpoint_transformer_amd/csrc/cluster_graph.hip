@@ -92,7 +92,8 @@ __global__ void emit_edges_kernel(const uint32_t* __restrict__ lo, const uint32_
 }
 
 struct Plan {
-  size_t off_lo, off_hi, off_key, off_flag, off_sort, total;
+  size_t off_lo, off_hi, off_key, off_flag, off_sort, off_part, total;
+  int64_t part_cap;
 };
 
 static Plan make_plan(int64_t m) {
@@ -104,6 +105,9 @@ static Plan make_plan(int64_t m) {
   p.off_key = o;  o += align_up((size_t)mm * 4, 256);
   p.off_flag = o; o += align_up((size_t)(mm + 1) * 4, 256);
   p.off_sort = o; o += RadixScratch::bytes(m + 1);
+  p.off_part = o; o += scan_part_bytes(mm + 1);   // scan of flag[0..m]: the sort's partials only
+                                                  // cover its digit histograms
+  p.part_cap = (int64_t)((o - p.off_part) / 4);
   p.total = o;
   return p;
 }
@@ -206,6 +210,7 @@ extern "C" int spt_cluster_graph_edges(const int64_t* neighbors, const float* di
   uint32_t* hi = (uint32_t*)(base + p.off_hi);
   uint32_t* key = (uint32_t*)(base + p.off_key);
   uint32_t* flag = (uint32_t*)(base + p.off_flag);
+  uint32_t* part = (uint32_t*)(base + p.off_part);
   RadixScratch s;
   s.carve(base + p.off_sort, m + 1);
 
@@ -216,13 +221,16 @@ extern "C" int spt_cluster_graph_edges(const int64_t* neighbors, const float* di
   // lexicographic (lo, hi): LSD = stable sort by hi, then stable sort by lo
   const int nb = bits_for(S + 1);
   const uint32_t *ks, *vs;
-  radix_sort_pairs<2>(nullptr, hi, nullptr, m, nb, s, nullptr, &ks, &vs, stream);
+  SPT_CHECK_ARG(radix_sort_pairs<2>(nullptr, hi, nullptr, m, nb, s, nullptr, &ks, &vs, stream) == 0,
+                "scan partials do not fit their region");
   gather_u32_kernel<<<g, 256, 0, stream>>>(lo, vs, m, key);
   RadixScratch s2 = s;
   if (vs == s.v0) { s2.v0 = s.v1; s2.v1 = s.v0; }
-  radix_sort_pairs<0>(nullptr, key, vs, m, nb, s2, nullptr, &ks, &vs, stream);
+  SPT_CHECK_ARG(radix_sort_pairs<0>(nullptr, key, vs, m, nb, s2, nullptr, &ks, &vs, stream) == 0,
+                "scan partials do not fit their region");
   run_heads_kernel<<<stream_grid(m + 1, 256), 256, 0, stream>>>(lo, hi, vs, m, S, flag);
-  device_exclusive_scan(flag, m + 1, s.part, stream);
+  SPT_CHECK_ARG(device_exclusive_scan(flag, m + 1, part, p.part_cap, stream) == 0,
+                "scan partials do not fit their region");
   emit_edges_kernel<<<g, 256, 0, stream>>>(lo, hi, vs, flag, distances, m, S, m, edges,
                                            edge_dist, count);
   SPT_CHECK_LAUNCH();

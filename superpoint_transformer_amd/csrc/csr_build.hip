@@ -42,8 +42,9 @@ extern "C" int spt_csr_build(const int64_t* idx, int64_t n, int64_t num_seg,
   RadixScratch s;
   s.carve((char*)ws, n);
   const uint32_t *ks, *vs;
-  radix_sort_pairs<1>(idx, nullptr, nullptr, n, bits_for(num_seg), s, (uint32_t*)perm, &ks,
-                      &vs, stream);
+  SPT_CHECK_ARG(radix_sort_pairs<1>(idx, nullptr, nullptr, n, bits_for(num_seg), s,
+                                    (uint32_t*)perm, &ks, &vs, stream) == 0,
+                "scan partials do not fit their region");
   rowptr_from_sorted_kernel<<<stream_grid(n + 1, 256), 256, 0, stream>>>(
       ks, n, num_seg, rowptr);
   SPT_CHECK_LAUNCH();

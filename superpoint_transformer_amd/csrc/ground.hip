@@ -474,6 +474,7 @@ static bool count_ok(int64_t n) { return n >= 0 && n < ((int64_t)1 << 31); }
 struct TrimPlan {
   int64_t words;
   size_t off_words, off_offs, off_part, total;
+  int64_t part_cap;
 };
 
 static TrimPlan trim_plan(int64_t n) {
@@ -482,7 +483,8 @@ static TrimPlan trim_plan(int64_t n) {
   size_t o = 0;
   p.off_words = o; o += align_up((size_t)(p.words + 1) * 4, 256);
   p.off_offs = o;  o += align_up((size_t)(p.words + 1) * 4, 256);
-  p.off_part = o;  o += align_up((size_t)ceil_div(p.words + 1, SCAN_TILE) * 4, 256);
+  p.off_part = o;  o += scan_part_bytes(p.words + 1);
+  p.part_cap = (int64_t)((o - p.off_part) / 4);
   p.total = o;
   return p;
 }
@@ -580,7 +582,8 @@ extern "C" int spt_ground_trim_f32(const float* pos, int64_t num_points, const f
     point_mask_kernel<<<stream_grid(n, THREADS), THREADS, 0, stream>>>(f, p.words, words);
   }
   popcount_kernel<<<stream_grid(p.words + 1, THREADS), THREADS, 0, stream>>>(words, p.words, offs);
-  device_exclusive_scan(offs, p.words + 1, part, stream);
+  SPT_CHECK_ARG(device_exclusive_scan(offs, p.words + 1, part, p.part_cap, stream) == 0,
+                "scan partials do not fit their region");
   emit_kernel<<<stream_grid(p.words, THREADS), THREADS, 0, stream>>>(words, offs, p.words,
                                                                      capacity, index, count);
   SPT_CHECK_LAUNCH();

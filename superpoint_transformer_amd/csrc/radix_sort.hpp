@@ -132,6 +132,29 @@ constexpr int SCAN_THREADS = 256;
 constexpr int SCAN_ITEMS = 16;
 constexpr int SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;
 
+// Partials of a scan over m values: one u32 per SCAN_TILE chunk.  The ONLY formula for that
+// region - every plan that feeds device_exclusive_scan sizes its partials with it, for the
+// longest array it scans.
+static inline int64_t scan_part_entries(int64_t m) { return ceil_div(m > 0 ? m : 1, SCAN_TILE); }
+static inline size_t scan_part_bytes(int64_t m) {
+  return align_up((size_t)scan_part_entries(m) * 4, 256);
+}
+
+// The common scratch of "flag / count array of m u32 values, scanned in place": the array, then
+// its partials.  `part_cap` is what the layout reserved, in entries - the capacity a caller
+// hands to device_exclusive_scan.
+struct ScanPlan {
+  size_t off_part, total;
+  int64_t part_cap;
+};
+static inline ScanPlan scan_plan(int64_t m) {
+  ScanPlan p;
+  p.off_part = align_up((size_t)(m > 0 ? m : 1) * 4, 256);
+  p.total = p.off_part + scan_part_bytes(m);
+  p.part_cap = (int64_t)((p.total - p.off_part) / 4);
+  return p;
+}
+
 __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v,
                                                          uint32_t* total) {
   __shared__ uint32_t wsum[SCAN_THREADS / 64];
@@ -255,15 +278,18 @@ static inline int bits_for(int64_t num_seg) {
 }
 
 // Scratch of one sort: two key buffers, two value buffers, per-workgroup digit
-// histograms and scan partials.  `bytes(n)` is what `carve` consumes.
+// histograms and scan partials.  `bytes(n)` is what `carve` consumes.  `part` holds
+// `part_cap` entries: enough for the digit histograms of a sort of n keys and for nothing
+// longer - a caller that scans another array brings partials of its own.
 struct RadixScratch {
   uint32_t *k0, *k1, *v0, *v1, *hist, *part;
+  int64_t part_cap;
   static size_t bytes(int64_t n) {
     const int64_t m = n > 0 ? n : 1;
     const int nblocks = (int)ceil_div(m, SORT_TILE);
     const int64_t hist_len = (int64_t)MAX_BINS * nblocks;
     return 4 * align_up((size_t)m * 4, 256) + align_up((size_t)hist_len * 4, 256) +
-           align_up((size_t)ceil_div(hist_len, SCAN_TILE) * 4, 256);
+           scan_part_bytes(hist_len);
   }
   char* carve(char* base, int64_t n) {
     const int64_t m = n > 0 ? n : 1;
@@ -275,26 +301,32 @@ struct RadixScratch {
     v0 = (uint32_t*)base; base += nb;
     v1 = (uint32_t*)base; base += nb;
     hist = (uint32_t*)base; base += align_up((size_t)hist_len * 4, 256);
-    part = (uint32_t*)base; base += align_up((size_t)ceil_div(hist_len, SCAN_TILE) * 4, 256);
+    part = (uint32_t*)base; base += scan_part_bytes(hist_len);
+    part_cap = (int64_t)(scan_part_bytes(hist_len) / 4);
     return base;
   }
 };
 
-// In-place exclusive scan of m u32 values (3 launches).
-static inline void device_exclusive_scan(uint32_t* data, int64_t m, uint32_t* part,
-                                         hipStream_t stream) {
-  const int nch = (int)ceil_div(m > 0 ? m : 1, SCAN_TILE);
+// In-place exclusive scan of m u32 values (3 launches).  `part` has room for `part_cap`
+// entries; the scan writes scan_part_entries(m) of them.  Returns 0, or -1 WITHOUT launching
+// anything when the partials would not fit (callers: SPT_CHECK_ARG on the result).
+static inline int device_exclusive_scan(uint32_t* data, int64_t m, uint32_t* part,
+                                        int64_t part_cap, hipStream_t stream) {
+  if (scan_part_entries(m) > part_cap) return -1;
+  const int nch = (int)scan_part_entries(m);
   scan_reduce_kernel<<<nch, SCAN_THREADS, 0, stream>>>(data, m, part);
   scan_partials_kernel<<<1, SCAN_THREADS, 0, stream>>>(part, nch);
   scan_apply_kernel<<<nch, SCAN_THREADS, 0, stream>>>(data, m, part);
+  return 0;
 }
 
 // Sort n pairs by the low `nbits` bits of the key.  MODE selects the first-pass
 // source (see top).  The last pass writes its values to `final_vals` when given
 // (else into the scratch); returns the sorted keys / values through the out
-// pointers.  nbits >= 1, n >= 1.
+// pointers.  nbits >= 1, n >= 1.  Returns 0, or -1 when the scratch's partials are too small
+// for a pass's histogram (nothing of that pass is launched).
 template <int MODE>
-static inline void radix_sort_pairs(const int64_t* idx64, const uint32_t* keys32,
+static inline int radix_sort_pairs(const int64_t* idx64, const uint32_t* keys32,
                                     const uint32_t* vals32, int64_t n, int nbits,
                                     RadixScratch& s, uint32_t* final_vals,
                                     const uint32_t** keys_sorted,
@@ -302,6 +334,7 @@ static inline void radix_sort_pairs(const int64_t* idx64, const uint32_t* keys32
   const int nblocks = (int)ceil_div(n, SORT_TILE);
   const int passes = (nbits + 7) / 8;
   const int per = (nbits + passes - 1) / passes;   // balanced digits, e.g. 19 -> 7+6+6
+  if (scan_part_entries((int64_t)(1 << per) * nblocks) > s.part_cap) return -1;  // widest pass
   uint32_t* kbuf[2] = {s.k0, s.k1};
   uint32_t* vbuf[2] = {s.v0, s.v1};
   const uint32_t* kin = keys32;
@@ -316,13 +349,13 @@ static inline void radix_sort_pairs(const int64_t* idx64, const uint32_t* keys32
     if (pass == 0) {
       radix_hist_kernel<MODE><<<nblocks, SORT_THREADS, 0, stream>>>(
           idx64, kin, n, shift, bits, s.hist, nblocks);
-      device_exclusive_scan(s.hist, hl, s.part, stream);
+      if (device_exclusive_scan(s.hist, hl, s.part, s.part_cap, stream)) return -1;
       radix_scatter_kernel<MODE><<<nblocks, SORT_THREADS, 0, stream>>>(
           idx64, kin, vin, n, shift, bits, s.hist, nblocks, kout, vout);
     } else {
       radix_hist_kernel<0><<<nblocks, SORT_THREADS, 0, stream>>>(
           nullptr, kin, n, shift, bits, s.hist, nblocks);
-      device_exclusive_scan(s.hist, hl, s.part, stream);
+      if (device_exclusive_scan(s.hist, hl, s.part, s.part_cap, stream)) return -1;
       radix_scatter_kernel<0><<<nblocks, SORT_THREADS, 0, stream>>>(
           nullptr, kin, vin, n, shift, bits, s.hist, nblocks, kout, vout);
     }
@@ -332,6 +365,7 @@ static inline void radix_sort_pairs(const int64_t* idx64, const uint32_t* keys32
   }
   *keys_sorted = kin;
   *vals_sorted = vin;
+  return 0;
 }
 
 }  // namespace spt

@@ -103,7 +103,8 @@ __global__ void take_samples_kernel(const uint32_t* __restrict__ skeys,
 }
 
 struct Plan {
-  size_t off_keys, off_rowptr, off_cnt, off_size, off_sort, total;
+  size_t off_keys, off_rowptr, off_cnt, off_size, off_sort, off_part, total;
+  int64_t part_cap;
 };
 
 static Plan make_plan(int64_t n, int64_t num_seg) {
@@ -115,6 +116,9 @@ static Plan make_plan(int64_t n, int64_t num_seg) {
   p.off_cnt = o;    o += align_up((size_t)(num_seg + 1) * 4, 256);
   p.off_size = o;   o += align_up((size_t)(num_seg + 1) * 4, 256);
   p.off_sort = o;   o += RadixScratch::bytes(n);
+  p.off_part = o;   o += scan_part_bytes(num_seg + 1);   // scan of cnt[0..num_seg]: the sort's
+                                                         // partials are sized from n alone
+  p.part_cap = (int64_t)((o - p.off_part) / 4);
   p.total = o;
   return p;
 }
@@ -147,6 +151,7 @@ extern "C" int spt_sparse_sample(const int64_t* idx, int64_t n, int64_t num_seg,
   int32_t* rowptr = (int32_t*)(base + p.off_rowptr);
   uint32_t* cnt = (uint32_t*)(base + p.off_cnt);
   uint32_t* size_all = mask ? (uint32_t*)(base + p.off_size) : nullptr;
+  uint32_t* part = (uint32_t*)(base + p.off_part);
   RadixScratch s;
   s.carve(base + p.off_sort, n);
 
@@ -154,7 +159,9 @@ extern "C" int spt_sparse_sample(const int64_t* idx, int64_t n, int64_t num_seg,
   if (n > 0) {
     // 1. shuffle: sort positions by a 32-bit random key
     random_keys_kernel<<<stream_grid(n, 256), 256, 0, stream>>>(seed, n, keys);
-    radix_sort_pairs<2>(nullptr, keys, nullptr, n, 32, s, nullptr, &ks, &vs, stream);
+    SPT_CHECK_ARG(radix_sort_pairs<2>(nullptr, keys, nullptr, n, 32, s, nullptr, &ks, &vs,
+                                      stream) == 0,
+                  "scan partials do not fit their region");
     // 2. stable sort of the shuffled elements by segment (masked-out -> bucket num_seg)
     if (size_all) (void)hipMemsetAsync(size_all, 0, (size_t)(num_seg + 1) * 4, stream);
     segment_keys_kernel<<<stream_grid(n, 256), 256, 0, stream>>>(idx, mask, vs, n, num_seg,
@@ -163,15 +170,17 @@ extern "C" int spt_sparse_sample(const int64_t* idx, int64_t n, int64_t num_seg,
     // MODE 0 ping-pongs between them, starting from the OTHER buffer
     RadixScratch s2 = s;
     if (vs == s.v0) { s2.v0 = s.v1; s2.v1 = s.v0; }
-    radix_sort_pairs<0>(nullptr, keys, vs, n, bits_for(num_seg + 1), s2, nullptr, &ks, &vs,
-                        stream);
+    SPT_CHECK_ARG(radix_sort_pairs<0>(nullptr, keys, vs, n, bits_for(num_seg + 1), s2, nullptr,
+                                      &ks, &vs, stream) == 0,
+                  "scan partials do not fit their region");
   }
   rowptr_from_sorted_kernel<<<stream_grid(n + 1, 256), 256, 0, stream>>>(ks, n, num_seg + 1,
                                                                         rowptr);
   // 3. how many to take per segment, exclusive scan -> pointers
   sample_counts_kernel<<<stream_grid(num_seg + 1, 256), 256, 0, stream>>>(
       rowptr, size_all, num_seg, n_max, n_min, cnt);
-  device_exclusive_scan(cnt, num_seg + 1, s.part, stream);
+  SPT_CHECK_ARG(device_exclusive_scan(cnt, num_seg + 1, part, p.part_cap, stream) == 0,
+                "scan partials do not fit their region");
   widen_ptr_kernel<<<stream_grid(num_seg + 1, 256), 256, 0, stream>>>(cnt, num_seg + 1, out_ptr);
   // 4. first cnt[s] shuffled members of every segment
   if (n > 0)

@@ -166,10 +166,6 @@ __global__ void ball_flags_kernel(const float* __restrict__ pos, int64_t n, floa
   }
 }
 
-static size_t scan_part_bytes(int64_t m) {
-  return align_up((size_t)ceil_div(m > 0 ? m : 1, SCAN_TILE) * 4, 256);
-}
-
 }  // namespace sel
 }  // namespace spt
 
@@ -190,7 +186,7 @@ extern "C" int spt_index_inverse(const int64_t* idx, int64_t k, int64_t n, int64
 
 extern "C" size_t spt_select_edges_workspace_bytes(int64_t num_edges) {
   if (num_edges < 0) return 0;
-  return align_up((size_t)(num_edges + 1) * 4, 256) + scan_part_bytes(num_edges + 1);
+  return scan_plan(num_edges + 1).total;
 }
 
 extern "C" int spt_select_edges(const int64_t* edge_index, int64_t num_edges, int64_t edge_stride,
@@ -206,12 +202,14 @@ extern "C" int spt_select_edges(const int64_t* edge_index, int64_t num_edges, in
     return 0;
   }
   SPT_CHECK_ARG(edge_index && inv && out_edges && idx_edge, "null pointer");
-  SPT_CHECK_ARG(ws && ws_bytes >= spt_select_edges_workspace_bytes(E), "workspace too small");
+  const ScanPlan sp = scan_plan(E + 1);
+  SPT_CHECK_ARG(ws && ws_bytes >= sp.total, "workspace too small");
   uint32_t* flag = (uint32_t*)ws;
-  uint32_t* part = (uint32_t*)((char*)ws + align_up((size_t)(E + 1) * 4, 256));
+  uint32_t* part = (uint32_t*)((char*)ws + sp.off_part);
   edge_flags_kernel<<<stream_grid(E + 1, 256), 256, 0, stream>>>(edge_index, E, edge_stride, inv,
                                                                 n, flag);
-  device_exclusive_scan(flag, E + 1, part, stream);
+  SPT_CHECK_ARG(device_exclusive_scan(flag, E + 1, part, sp.part_cap, stream) == 0,
+                "scan partials do not fit their region");
   edge_emit_kernel<<<stream_grid(E, 256), 256, 0, stream>>>(edge_index, E, edge_stride, inv, flag,
                                                            out_stride, out_edges, idx_edge, count);
   SPT_CHECK_LAUNCH();
@@ -255,7 +253,7 @@ __global__ __launch_bounds__(256) void dense_emit_kernel(const int64_t* __restri
 
 extern "C" size_t spt_neighbors_dense_to_csr_workspace_bytes(int64_t n) {
   if (n < 0) return 0;
-  return align_up((size_t)(n + 1) * 4, 256) + scan_part_bytes(n + 1);
+  return scan_plan(n + 1).total;
 }
 
 extern "C" int spt_neighbors_dense_to_csr(const int64_t* nn, int64_t n, int k, int64_t* ptr,
@@ -264,13 +262,14 @@ extern "C" int spt_neighbors_dense_to_csr(const int64_t* nn, int64_t n, int k, i
   hipStream_t stream = (hipStream_t)stream_;
   SPT_CHECK_ARG(n >= 0 && k >= 0, "bad shape");
   SPT_CHECK_ARG((int64_t)n * k < ((int64_t)1 << 32) - 2, "more than 2^32 entries");
-  SPT_CHECK_ARG(ptr && ws && ws_bytes >= spt_neighbors_dense_to_csr_workspace_bytes(n),
-                "null pointer / workspace too small");
+  const ScanPlan sp = scan_plan(n + 1);
+  SPT_CHECK_ARG(ptr && ws && ws_bytes >= sp.total, "null pointer / workspace too small");
   SPT_CHECK_ARG(n == 0 || (sizes && (k == 0 || (nn && val))), "null pointer");
   uint32_t* cnt = (uint32_t*)ws;
-  uint32_t* part = (uint32_t*)((char*)ws + align_up((size_t)(n + 1) * 4, 256));
+  uint32_t* part = (uint32_t*)((char*)ws + sp.off_part);
   dense_count_kernel<<<stream_grid(n + 1, 256), 256, 0, stream>>>(nn, n, k, cnt, sizes);
-  device_exclusive_scan(cnt, n + 1, part, stream);
+  SPT_CHECK_ARG(device_exclusive_scan(cnt, n + 1, part, sp.part_cap, stream) == 0,
+                "scan partials do not fit their region");
   dense_emit_kernel<<<stream_grid(n + 1, 256), 256, 0, stream>>>(nn, n, k, cnt, ptr, val);
   SPT_CHECK_LAUNCH();
   return 0;
@@ -279,6 +278,7 @@ extern "C" int spt_neighbors_dense_to_csr(const int64_t* nn, int64_t n, int k, i
 namespace {
 struct ClusterPlan {
   size_t off_sizes, off_owner, off_present, off_tmp, off_part, total;
+  int64_t part_cap;
 };
 ClusterPlan cluster_plan(int64_t k, int64_t m, int64_t n_sub) {
   ClusterPlan p;
@@ -289,6 +289,7 @@ ClusterPlan cluster_plan(int64_t k, int64_t m, int64_t n_sub) {
   p.off_tmp = o;     o += align_up((size_t)(m > 0 ? m : 1) * 8, 256);
   const int64_t big = (k + 1 > n_sub + 1) ? k + 1 : n_sub + 1;
   p.off_part = o;    o += scan_part_bytes(big);
+  p.part_cap = (int64_t)(scan_part_bytes(big) / 4);
   p.total = o;
   return p;
 }
@@ -327,7 +328,8 @@ extern "C" int spt_cluster_select(const int64_t* pointers, const int64_t* points
                 "null pointer");
   // new pointers = exclusive scan of the selected sizes        (csr.py:343-346)
   selected_sizes_kernel<<<stream_grid(k + 1, 256), 256, 0, stream>>>(pointers, idx, k, sizes);
-  device_exclusive_scan(sizes, k + 1, part, stream);
+  SPT_CHECK_ARG(device_exclusive_scan(sizes, k + 1, part, p.part_cap, stream) == 0,
+                "scan partials do not fit their region");
   widen_kernel<<<stream_grid(k + 1, 256), 256, 0, stream>>>(sizes, k + 1, new_pointers);
   (void)hipMemsetAsync(present, 0, (size_t)(n_sub + 1) * 4, stream);
   // the number of copied points (newptr[k]) is only known on the device: launch over
@@ -336,11 +338,13 @@ extern "C" int spt_cluster_select(const int64_t* pointers, const int64_t* points
     const int g = stream_grid(M, 256);
     cluster_copy_kernel<<<g, 256, 0, stream>>>(pointers, points, idx, sizes, k, n_sub, tmp, owner,
                                                present);
-    device_exclusive_scan(present, n_sub + 1, part, stream);
+    SPT_CHECK_ARG(device_exclusive_scan(present, n_sub + 1, part, p.part_cap, stream) == 0,
+                  "scan partials do not fit their region");
     cluster_emit_kernel<<<g, 256, 0, stream>>>(tmp, owner, present, sizes, k, n_sub, new_points,
                                                sub_super);
   } else {
-    device_exclusive_scan(present, n_sub + 1, part, stream);
+    SPT_CHECK_ARG(device_exclusive_scan(present, n_sub + 1, part, p.part_cap, stream) == 0,
+                  "scan partials do not fit their region");
   }
   // idx_sub = the surviving sub points in ascending order      (cluster.py:130-131)
   compact_present_kernel<<<stream_grid(n_sub + 1, 256), 256, 0, stream>>>(present, n_sub, idx_sub,
@@ -351,7 +355,7 @@ extern "C" int spt_cluster_select(const int64_t* pointers, const int64_t* points
 
 extern "C" size_t spt_relabel_consecutive_workspace_bytes(int64_t n_range) {
   if (n_range < 0) return 0;
-  return align_up((size_t)(n_range + 1) * 4, 256) + scan_part_bytes(n_range + 1);
+  return scan_plan(n_range + 1).total;
 }
 
 extern "C" int spt_relabel_consecutive(const int64_t* values, const int64_t* gather, int64_t k,
@@ -361,16 +365,17 @@ extern "C" int spt_relabel_consecutive(const int64_t* values, const int64_t* gat
   hipStream_t stream = (hipStream_t)stream_;
   SPT_CHECK_ARG(k >= 0 && n_range >= 0 && n_range < ((int64_t)1 << 32) - 2, "bad shape");
   SPT_CHECK_ARG(count != nullptr, "count is null");
-  SPT_CHECK_ARG(ws && ws_bytes >= spt_relabel_consecutive_workspace_bytes(n_range),
-                "workspace too small");
+  const ScanPlan sp = scan_plan(n_range + 1);
+  SPT_CHECK_ARG(ws && ws_bytes >= sp.total, "workspace too small");
   SPT_CHECK_ARG(k == 0 || (values && new_values), "null pointer");
   SPT_CHECK_ARG(n_range == 0 || uniques, "uniques is null");
   uint32_t* present = (uint32_t*)ws;
-  uint32_t* part = (uint32_t*)((char*)ws + align_up((size_t)(n_range + 1) * 4, 256));
+  uint32_t* part = (uint32_t*)((char*)ws + sp.off_part);
   (void)hipMemsetAsync(present, 0, (size_t)(n_range + 1) * 4, stream);
   if (k > 0)
     mark_values_kernel<<<stream_grid(k, 256), 256, 0, stream>>>(values, gather, k, n_range, present);
-  device_exclusive_scan(present, n_range + 1, part, stream);
+  SPT_CHECK_ARG(device_exclusive_scan(present, n_range + 1, part, sp.part_cap, stream) == 0,
+                "scan partials do not fit their region");
   if (k > 0)
     relabel_kernel<<<stream_grid(k, 256), 256, 0, stream>>>(values, gather, k, n_range, present,
                                                             new_values);
@@ -382,7 +387,7 @@ extern "C" int spt_relabel_consecutive(const int64_t* values, const int64_t* gat
 
 extern "C" size_t spt_radius_ball_workspace_bytes(int64_t n) {
   if (n < 0) return 0;
-  return align_up((size_t)(n + 1) * 4, 256) + scan_part_bytes(n + 1);
+  return scan_plan(n + 1).total;
 }
 
 extern "C" int spt_radius_ball_f32(const float* pos, int64_t n, const float* center, float r,
@@ -392,13 +397,15 @@ extern "C" int spt_radius_ball_f32(const float* pos, int64_t n, const float* cen
   hipStream_t stream = (hipStream_t)stream_;
   SPT_CHECK_ARG(n >= 0 && n < ((int64_t)1 << 32) - 2 && r >= 0.f, "bad shape");
   SPT_CHECK_ARG(count && center, "null pointer");
-  SPT_CHECK_ARG(ws && ws_bytes >= spt_radius_ball_workspace_bytes(n), "workspace too small");
+  const ScanPlan sp = scan_plan(n + 1);
+  SPT_CHECK_ARG(ws && ws_bytes >= sp.total, "workspace too small");
   SPT_CHECK_ARG(n == 0 || (pos && out_idx), "null pointer");
   uint32_t* flag = (uint32_t*)ws;
-  uint32_t* part = (uint32_t*)((char*)ws + align_up((size_t)(n + 1) * 4, 256));
+  uint32_t* part = (uint32_t*)((char*)ws + sp.off_part);
   ball_flags_kernel<<<stream_grid(n + 1, 256), 256, 0, stream>>>(
       pos, n, center[0], center[1], center[2], cylindrical ? 0.f : 1.f, r, batch, batch_id, flag);
-  device_exclusive_scan(flag, n + 1, part, stream);
+  SPT_CHECK_ARG(device_exclusive_scan(flag, n + 1, part, sp.part_cap, stream) == 0,
+                "scan partials do not fit their region");
   compact_present_kernel<<<stream_grid(n + 1, 256), 256, 0, stream>>>(flag, n, out_idx, count);
   SPT_CHECK_LAUNCH();
   return 0;
