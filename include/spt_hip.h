@@ -1071,7 +1071,7 @@ int spt_fused_linear_pooled_supported(int K, int N);
 int spt_fused_linear_pooled_supported_ex(int K, int N, int mode);
 /* Tile staging of the split-bf16 / bf16 backward kernels: LDS-DMA (global_load_lds: one memory
  * round trip per 16-row tile, csrc/fused_mlp_dma.hip; default, where the (K, N) is built: 64->128,
- * 64->64, 32->64) or register-staged (csrc/fused_mlp.hip).  Same arithmetic, same summation order
+ * 64->64, 32->64, and 32->32 for dense f32 rows) or register-staged (csrc/fused_mlp.hip).  Same arithmetic, same summation order
  * inside a tile.  Process-wide: spt_fused_linear_bwd_use_dma(0 | 1) (< 0: query), returns the
  * previous setting; per call: OR SPT_FMLP_BWD_REGISTER_STAGED into the `mode` of the *_ex entries. */
 #define SPT_FMLP_BWD_REGISTER_STAGED 4
@@ -1085,6 +1085,11 @@ int spt_fused_linear_pooled_supported_ex(int K, int N, int mode);
 #define SPT_FMLP_X_BF16 16
 int spt_fused_linear_storage_supported(int K, int N);
 int spt_fused_linear_bwd_use_dma(int on);
+/* The staging the dense backward with gx of K -> N (K0 == 0), or the fold of K0 -> K under K -> N
+ * (K0 > 0, see spt_fused_linear_bwd_fold_supported), takes under `mode` and the process-wide switch:
+ * 1 = LDS-DMA, 0 = register-staged, -1 = the fold is not built.  The two stagings give the same
+ * bits, so this is how a caller or a test tells them apart. */
+int spt_fused_linear_bwd_route(int K0, int K, int N, int mode);
 /* Forward of matrix mode 1 (the default "f32"): 1 (default) = the f32 product as SIX bf16 products
  * of 3-way split operands on the bf16 matrix pipe (f32-exact: every dropped term is below 2^-24 of
  * its product), 0 = the f32 matrix pipe.  Process-wide; < 0 queries; returns the previous setting. */
@@ -1171,7 +1176,7 @@ int spt_fused_linear_bwd_runs_gn_f32(
  * of inside the upper layer's kernel, stores no gx and writes gW0 from its post launch (together
  * with the bottom norm's tables in prev_norm, which is required; W0 [K, K0] = the bottom weight).
  * _supported: 1 when the shape pair is built for the matrix mode - 12 -> 32 under 32 -> 64 (DMA-staged
- * backward) and 18 -> 32 under 32 -> 32, in the default f32 mode (f32-exact split forward, split-bf16
+ * backward) and 18 -> 32 under 32 -> 32 (DMA-staged or register-staged), in the default f32 mode (f32-exact split forward, split-bf16
  * backward; no bf16 storage). */
 int spt_fused_linear_bwd_fold_supported(int K0, int K, int N, int mode);
 int spt_fused_linear_bwd_runs_gn_fold_f32(

@@ -1845,8 +1845,9 @@ int fmlp_dma_bwd_launch(bool pooled, bool lo, const float* gy, const float* h, F
                         const int32_t* pos_seg, const float* gout, const int32_t* arg,
                         hipStream_t stream, bool s16 = false, int* gw_tabs = nullptr,
                         const float* x0 = nullptr, const float* fshift = nullptr,
-                        float* fold_partial = nullptr, int K0 = 0);
+                        float* fold_partial = nullptr, int K0 = 0, int blocks32 = 0);
 bool fmlp_dma_fold_supported(int K0, int K, int N);
+bool fmlp_dma_dense_only(int K, int N);
 int fmlp_fold_len(int K, int K0);
 }  // namespace spt
 
@@ -2237,6 +2238,9 @@ static int fmlp_bwd_impl(bool pooled, const float* gy, const float* gout, const 
   }
   float* fold_tabs = nullptr;
   float* fold_shift = nullptr;
+  // the DMA-staged 32 -> 32 runs on the grid of the register-staged <8, 2> launch
+  const int blocks32 = (K == 32 && N == 32) ? cap_grid(grid_for_nw(max_rows, 4, 4), 4) : 0;
+  const bool dma_dense_only = fmlp_dma_dense_only(K, N);
   int per_run = 0;                              // wave records per run (statistics tables)
   int gw_tabs = 0;                              // weight-gradient tables per run (one per wave, or
                                                 // one per workgroup: fmlp_bf_wg_reduce)
@@ -2288,7 +2292,7 @@ static int fmlp_bwd_impl(bool pooled, const float* gy, const float* gout, const 
           gy, h, 0, 0, am, scale, bias, slope, c1, c2, c3, xprev, K, pre_am, pre_scale,          \
           pre_bias, pre_slope, W, nullptr, gwp, nullptr, rt);                                    \
   }
-    if (x16 && gx && fmlp_dma_of(mode) && fmlp_dma_supported(K, N)) {
+    if (x16 && gx && fmlp_dma_of(mode) && fmlp_dma_supported(K, N) && !dma_dense_only) {
       per_run = fmlp_dma_bwd_launch(pooled, false, gy, h, rt, max_rows, N, am, scale, bias, slope, c1,
                                     c2, c3, xprev, K, pre_am, pre_scale, pre_bias, pre_slope, W, gx,
                                     gwp, pstp, perm, pos_seg, gout, arg, stream, true, &gw_tabs);
@@ -2313,7 +2317,7 @@ static int fmlp_bwd_impl(bool pooled, const float* gy, const float* gout, const 
       per_run = fmlp_dma_bwd_launch(false, true, gy, h, rt, max_rows, N, am, scale, bias, slope, c1, c2,
                                     c3, xprev, K, pre_am, pre_scale, pre_bias, pre_slope, W, nullptr,
                                     gwp, pstp, nullptr, nullptr, nullptr, nullptr, stream, false,
-                                    &gw_tabs, fold_x0, fold_shift, fold_tabs, fold_K0);
+                                    &gw_tabs, fold_x0, fold_shift, fold_tabs, fold_K0, blocks32);
     } else if (fold_K0 == 18 && k4 == 8 && nbk == 2) {
       // the edge MLP's 18 -> 32 under 32 -> 32: the grid of the plain <8, 2> launch
       constexpr int NWB = 4;
@@ -2328,10 +2332,12 @@ static int fmlp_bwd_impl(bool pooled, const float* gy, const float* gout, const 
       per_run = gx_ * nwv;
     }
     SPT_CHECK_ARG((size_t)gw_tabs * nr <= FOLD_MAX_TABS, "fold: more tables than the workspace layout holds");
-  } else if (g_fmlp_split_bf16 && gx && fmlp_dma_of(mode) && fmlp_dma_supported(K, N)) {
+  } else if (g_fmlp_split_bf16 && gx && fmlp_dma_of(mode) && fmlp_dma_supported(K, N) &&
+             !(pooled && dma_dense_only)) {
     per_run = fmlp_dma_bwd_launch(pooled, g_fmlp_mode != 3, gy, h, rt, max_rows, N, am, scale, bias,
                                   slope, c1, c2, c3, xprev, K, pre_am, pre_scale, pre_bias, pre_slope,
-                                  W, gx, gwp, pstp, perm, pos_seg, gout, arg, stream, false, &gw_tabs);
+                                  W, gx, gwp, pstp, perm, pos_seg, gout, arg, stream, false, &gw_tabs,
+                                  nullptr, nullptr, nullptr, 0, blocks32);
   } else if (pooled) {
     SPT_FMLP_POOLED_SHAPES(XP)
     per_run = gx_ * nwv;
@@ -2511,6 +2517,19 @@ extern "C" int spt_fused_linear_bwd_fold_supported(int K0, int K, int N, int mod
   // (the Gram stands in for o^T x0: the forward must have formed h0 = W0 x0 to f32 accuracy)
   return m == 1 && g_fmlp_x3 &&
          ((fmlp_dma_of(mode) && fmlp_dma_fold_supported(K0, K, N)) || (K0 == 18 && K == 32 && N == 32));
+}
+// Which kernel the dense backward with gx of K -> N (K0 == 0), or the fold of K0 -> K under it
+// (K0 > 0), runs under `mode` and the process-wide switch: 1 = LDS-DMA staged, 0 = register-staged
+// (or f32 matrix pipe), -1 = the fold is not built.  Follows fmlp_bwd_impl's dispatch.
+extern "C" int spt_fused_linear_bwd_route(int K0, int K, int N, int mode) {
+  const int m = fmlp_mode_of(mode);
+  if (K0 > 0) {
+    if (!spt_fused_linear_bwd_fold_supported(K0, K, N, mode)) return -1;
+    return fmlp_dma_of(mode) && fmlp_dma_fold_supported(K0, K, N);
+  }
+  if (mode >= 0 && (mode & (SPT_FMLP_H_BF16 | SPT_FMLP_X_BF16)))
+    return (mode & SPT_FMLP_X_BF16) && fmlp_dma_of(mode) && fmlp_dma_supported(K, N) && !fmlp_dma_dense_only(K, N);
+  return m >= 1 && fmlp_dma_of(mode) && fmlp_dma_supported(K, N);
 }
 extern "C" int spt_fused_linear_bwd_runs_gn_fold_f32(
     const float* gy, const float* h, int nruns, const int64_t* run_r0, const int64_t* run_r1,

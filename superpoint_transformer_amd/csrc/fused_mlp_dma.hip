@@ -64,6 +64,16 @@ __device__ __forceinline__ void lds_dma16(const void* g, float* lds) {
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off"
                :: "s"(a), "v"(g) : "memory");
 }
+// one dword per lane (256 B per instruction): global addresses need 4-byte alignment only
+__device__ __forceinline__ void lds_dma4(const void* g, float* lds) {
+#if SPT_FDMA_SKIP & 32
+  return;
+#endif
+  const unsigned a = __builtin_amdgcn_readfirstlane(
+      (unsigned)(size_t)((__attribute__((address_space(3))) void*)lds));
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, off"
+               :: "s"(a), "v"(g) : "memory");
+}
 __device__ __forceinline__ void wait_vm0() {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -135,11 +145,15 @@ __device__ __forceinline__ int pick_lane(int v, int base, int sel) {
 // stands in for Bm = o^T (x0 - s): the bottom layer has no bias and no norm in front, o = W0 x0 - am,
 // so Bm = W0 G' - am (x) sx with G' the Gram block and sx = column FOLD_K0 of G (the ones column;
 // G[FOLD_K0][FOLD_K0] = the row count).  gx is not stored; the post launch (fused_mlp.hip) undoes
-// the shift in f64 and writes gW0.  One table of fold_len(K, FK0) floats per workgroup: A [K][16] | G [16][16].
+// the shift in f64 and writes gW0.  One table of fold_len(K, FK0) floats per workgroup: A [K][ZP] | G [ZP][ZP].
+// Staging x0: a tile's 16 rows are one contiguous block of 64 FK0 bytes.  Rows of whole 16-byte
+// chunks that fill at most 1 KB (FK0 = 12) travel as ONE dwordx4 DMA instruction.  Other widths
+// (FK0 = 18: 72-byte rows, the block starts 8-byte aligned at odd rows) travel as dword DMA
+// instructions, 256 B each, legal at the 4-byte alignment of the elements, in every tile alike.
 // (the table layout - A [K][ZP] | G [ZP][ZP], ZP = K0 + 1 padded to whole 16-column blocks - is
 // shared with fused_mlp.hip's register-staged FOLD instance and its post launch)
 constexpr int fold_len(int K, int K0) { return (K + (K0 + 16) / 16 * 16) * ((K0 + 16) / 16 * 16); }
-// FK0 = K0 of the folded bottom layer (0: no fold); rows of whole 16-byte chunks, one 1 KB block per tile
+// FK0 = K0 of the folded bottom layer (0: no fold)
 template <int K, int N, int NW, int OCC, bool LO, bool POOLED, bool S16 = false, int FK0 = 0>
 __global__ __launch_bounds__(NW * 64, OCC) void bwd_dma_kernel(
     const float* __restrict__ gy, const float* __restrict__ h, int64_t r0, int64_t r1,
@@ -156,7 +170,11 @@ __global__ __launch_bounds__(NW * 64, OCC) void bwd_dma_kernel(
   constexpr bool FOLD = FK0 > 0;
   constexpr int FOLD_K0 = FK0;
   static_assert(!FOLD || (!POOLED && !S16), "the fold reads dense f32 rows");
-  static_assert(!FOLD || (FK0 % 4 == 0 && FK0 < 16 && TR * FK0 * 4 <= 1024), "x0 tile: one DMA block, one k block");
+  constexpr int ZP = (FK0 + 16) / 16 * 16, ZB = ZP / 16;     // z = [x0 - s | 1 | 0 ..]: ZB 16-column blocks
+  constexpr bool X0_DMA16 = FK0 % 4 == 0 && TR * FK0 * 4 <= 1024;   // one dwordx4 instruction per tile
+  constexpr int X0N = X0_DMA16 ? 1 : (TR * FK0 + 63) / 64;           // else: dword instructions per tile
+  constexpr int X0LEN = X0_DMA16 ? 256 : 64 * X0N;
+  static_assert(!FOLD || ZP <= 32, "the shift table holds 32 columns");
   constexpr int NC = N / 4, KC = K / 4, NBK = N / 16, KB = K / 16, NS = N / 32;
   if (rt.n > 0) {                           // multi-run launch (common.hpp): blockIdx.y = run
     const int run_ = blockIdx.y, gph_ = rt.g[run_];
@@ -182,9 +200,9 @@ __global__ __launch_bounds__(NW * 64, OCC) void bwd_dma_kernel(
   __shared__ __attribute__((aligned(16))) __bf16 wt_hi[K * LDT];
   __shared__ __attribute__((aligned(16))) __bf16 wt_lo[LO ? K * LDT : 8];
   __shared__ __attribute__((aligned(16))) float pt[3 * K];      // previous norm: am | sc | bs
-  // FOLD: the tile's 16 rows of x0 are one contiguous 768-byte block: ONE DMA instruction (1 KB)
-  __shared__ __attribute__((aligned(16))) float x0b[FOLD ? NW : 1][FOLD ? 256 : 4];
-  __shared__ float fsh[16];                                     // FOLD: the graph's shift
+  // FOLD: the tile's 16 rows of x0 are one contiguous block of 64 FK0 bytes
+  __shared__ __attribute__((aligned(16))) float x0b[FOLD ? NW : 1][FOLD ? X0LEN : 4];
+  __shared__ float fsh[32];                                     // FOLD: the graph's shift
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int g = lane >> 4, c = lane & 15;
@@ -201,7 +219,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void bwd_dma_kernel(
     if constexpr (LO) wt_lo[k * LDT + n] = (__bf16)(w - (float)hh);
   }
   if constexpr (FOLD) {
-    if (threadIdx.x < 16) fsh[threadIdx.x] = threadIdx.x < FOLD_K0 ? fshift[threadIdx.x] : 0.f;
+    if (threadIdx.x < 32) fsh[threadIdx.x] = threadIdx.x < FOLD_K0 ? fshift[threadIdx.x] : 0.f;
   }
   for (int i = threadIdx.x; i < K; i += NW * 64) {
     pt[i] = pre ? pam[i] : 0.f;
@@ -218,10 +236,15 @@ __global__ __launch_bounds__(NW * 64, OCC) void bwd_dma_kernel(
   double p1[KB], p2[KB];
 #pragma unroll
   for (int kb = 0; kb < KB; ++kb) p1[kb] = p2[kb] = 0.0;
-  // FOLD: FA[kb][r] = A[16 kb + 4 g + r][c], FG[r] = G[4 g + r][c]
-  f32x4 FA[FOLD ? KB : 1], FG = (f32x4){0.f, 0.f, 0.f, 0.f};
+  // FOLD: FA[kb][zb][r] = A[16 kb + 4 g + r][16 zb + c], FG[za][zb][r] = G[16 za + 4 g + r][16 zb + c]
+  f32x4 FA[FOLD ? KB : 1][ZB], FG[ZB][ZB];
 #pragma unroll
-  for (int kb = 0; kb < (FOLD ? KB : 1); ++kb) FA[kb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int zb = 0; zb < ZB; ++zb) {
+#pragma unroll
+    for (int kb = 0; kb < (FOLD ? KB : 1); ++kb) FA[kb][zb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int za = 0; za < ZB; ++za) FG[za][zb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
   float* X0B = x0b[FOLD ? wid : 0];
 
   const int64_t ntiles = (r1 - r0 + TR - 1) / TR;
@@ -326,8 +349,19 @@ __global__ __launch_bounds__(NW * 64, OCC) void bwd_dma_kernel(
       // lane L < 48: floats [4 L, 4 L + 4) of the tile's block; the other lanes, and a short last
       // tile's lanes past its rows, re-read the block's last whole chunk (never past row r1 - 1)
       const int cnt = (int)((r1 - row0) < TR ? (r1 - row0) : TR);
-      const int last = cnt * FOLD_K0 - 4;
-      lds_dma16(x0 + row0 * FOLD_K0 + (4 * ln < last ? 4 * ln : last), X0B);
+      if constexpr (X0_DMA16) {
+        const int last = cnt * FOLD_K0 - 4;
+        lds_dma16(x0 + row0 * FOLD_K0 + (4 * ln < last ? 4 * ln : last), X0B);
+      } else {
+        // instruction i, lane L: float 64 i + L of the block; floats past the tile's rows re-read
+        // its last one (never past row r1 - 1)
+        const int last = cnt * FOLD_K0 - 1;
+#pragma unroll
+        for (int i = 0; i < X0N; ++i) {
+          const int f = 64 * i + ln;
+          lds_dma4(x0 + row0 * FOLD_K0 + (f < last ? f : last), X0B + 64 * i);
+        }
+      }
     }
     if constexpr (S16) {
       const uint16_t* xb = reinterpret_cast<const uint16_t*>(xprev) + (POOLED ? 0 : row0 * K);
@@ -489,18 +523,26 @@ __global__ __launch_bounds__(NW * 64, OCC) void bwd_dma_kernel(
     // (f64 per element, like the register-staged kernel: sum g' and sum g' o' cancel to a small
     //  fraction of their terms - f32 partial sums over the 4 rows of a lane moved the input
     //  gradient three layers down by more than 1e-5 of its entries)
-    bf16x4 X0h, X0l;                                 // FOLD: [x0 - s | 1 | 0 0 0] of this lane's rows
+    bf16x4 X0h[ZB], X0l[ZB];                         // FOLD: [x0 - s | 1 | 0 ..] of this lane's rows
     if constexpr (FOLD) {
-      float x0v[4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int rr = 4 * g + r;
-        const float xr = X0B[rr * FOLD_K0 + (c < FOLD_K0 ? c : 0)];
-        const float one = (c == FOLD_K0) ? 1.f : 0.f;
-        x0v[r] = (rr < cnt) ? ((c < FOLD_K0) ? xr - fsh[c] : one) : 0.f;
+      for (int zb = 0; zb < ZB; ++zb) {
+        const int col = 16 * zb + c;
+        float x0v[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int rr = 4 * g + r;
+          const float xr = X0B[rr * FOLD_K0 + (col < FOLD_K0 ? col : 0)];
+          const float one = (col == FOLD_K0) ? 1.f : 0.f;
+          x0v[r] = (rr < cnt) ? ((col < FOLD_K0) ? xr - fsh[col] : one) : 0.f;
+        }
+        split_bf16<4>(x0v, X0h[zb], X0l[zb]);
       }
-      split_bf16<4>(x0v, X0h, X0l);
-      FG = mfma3_16<LO>(X0h, X0l, X0h, X0l, FG);
+#pragma unroll
+      for (int za = 0; za < ZB; ++za)
+#pragma unroll
+        for (int zb = 0; zb < ZB; ++zb)
+          FG[za][zb] = mfma3_16<LO>(X0h[za], X0l[za], X0h[zb], X0l[zb], FG[za][zb]);
     }
 #pragma unroll
     for (int kb = 0; kb < KB; ++kb) {
@@ -526,7 +568,8 @@ __global__ __launch_bounds__(NW * 64, OCC) void bwd_dma_kernel(
       if constexpr (FOLD) {
         bf16x4 ah, al;
         split_bf16<4>(ggv, ah, al);
-        FA[kb] = mfma3_16<LO>(ah, al, X0h, X0l, FA[kb]);
+#pragma unroll
+        for (int zb = 0; zb < ZB; ++zb) FA[kb][zb] = mfma3_16<LO>(ah, al, X0h[zb], X0l[zb], FA[kb][zb]);
       }
     }
     if constexpr (!FOLD) {
@@ -594,31 +637,40 @@ __global__ __launch_bounds__(NW * 64, OCC) void bwd_dma_kernel(
     for (int w = 1; w < NW; ++w) {
       if (wid == w) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
+        for (int zb = 0; zb < ZB; ++zb)
 #pragma unroll
-          for (int kb = 0; kb < KB; ++kb) red[(16 * kb + 4 * g + r) * 16 + c] = FA[kb][r];
-          red[(K + 4 * g + r) * 16 + c] = FG[r];
-        }
+          for (int r = 0; r < 4; ++r) {
+#pragma unroll
+            for (int kb = 0; kb < KB; ++kb) red[(16 * kb + 4 * g + r) * ZP + 16 * zb + c] = FA[kb][zb][r];
+#pragma unroll
+            for (int za = 0; za < ZB; ++za) red[(K + 16 * za + 4 * g + r) * ZP + 16 * zb + c] = FG[za][zb][r];
+          }
       }
       __syncthreads();
       if (wid == 0) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
+        for (int zb = 0; zb < ZB; ++zb)
 #pragma unroll
-          for (int kb = 0; kb < KB; ++kb) FA[kb][r] += red[(16 * kb + 4 * g + r) * 16 + c];
-          FG[r] += red[(K + 4 * g + r) * 16 + c];
-        }
+          for (int r = 0; r < 4; ++r) {
+#pragma unroll
+            for (int kb = 0; kb < KB; ++kb) FA[kb][zb][r] += red[(16 * kb + 4 * g + r) * ZP + 16 * zb + c];
+#pragma unroll
+            for (int za = 0; za < ZB; ++za) FG[za][zb][r] += red[(K + 16 * za + 4 * g + r) * ZP + 16 * zb + c];
+          }
       }
       __syncthreads();
     }
     if (wid == 0) {
       float* fp = fold_partial + (size_t)blockIdx.x * FLN;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
+      for (int zb = 0; zb < ZB; ++zb)
 #pragma unroll
-        for (int kb = 0; kb < KB; ++kb) fp[(16 * kb + 4 * g + r) * 16 + c] = FA[kb][r];
-        fp[(K + 4 * g + r) * 16 + c] = FG[r];
-      }
+        for (int r = 0; r < 4; ++r) {
+#pragma unroll
+          for (int kb = 0; kb < KB; ++kb) fp[(16 * kb + 4 * g + r) * ZP + 16 * zb + c] = FA[kb][zb][r];
+#pragma unroll
+          for (int za = 0; za < ZB; ++za) fp[(K + 16 * za + 4 * g + r) * ZP + 16 * zb + c] = FG[za][zb][r];
+        }
     }
   }
   if (pstat_partial) {
@@ -637,15 +689,18 @@ __global__ __launch_bounds__(NW * 64, OCC) void bwd_dma_kernel(
 
 }  // namespace fdma
 
-// (K, N) with a DMA-staged backward: the point MLP's 64 -> 128, 32 -> 64 and (panoptic) 64 -> 64
-// (K0, K, N) of a bottom layer K0 -> K folded into the DMA-staged backward of K -> N above it
+// (K0, K, N) of a bottom layer K0 -> K folded into the DMA-staged backward of K -> N above it:
+// the point MLP's 12 -> 32 under 32 -> 64, the edge MLP's 18 -> 32 under 32 -> 32
 bool fmlp_dma_fold_supported(int K0, int K, int N) {
-  return K0 == 12 && K == 32 && N == 64;
+  return (K0 == 12 && K == 32 && N == 64) || (K0 == 18 && K == 32 && N == 32);
 }
 int fmlp_fold_len(int K, int K0) { return fdma::fold_len(K, K0); }
+// (K, N) with a DMA-staged backward: the point MLP's 64 -> 128, 32 -> 64, (panoptic) 64 -> 64 and
+// the edge MLP's 32 -> 32 (dense f32 rows only: fmlp_dma_dense_only)
 bool fmlp_dma_supported(int K, int N) {
-  return (K == 64 && N == 128) || (K == 32 && N == 64) || (K == 64 && N == 64);
+  return (K == 64 && N == 128) || (K == 32 && N == 64) || (K == 64 && N == 64) || (K == 32 && N == 32);
 }
+bool fmlp_dma_dense_only(int K, int N) { return K == 32 && N == 32; }
 
 bool fmlp_dma_fold_supported(int K0, int K, int N);
 // Launches the layer's backward; returns the number of per-wave partial tables written
@@ -660,10 +715,33 @@ int fmlp_dma_bwd_launch(bool pooled, bool lo, const float* gy, const float* h, F
                         float* gw_partial, double* pstat_partial, const int32_t* perm,
                         const int32_t* pos_seg, const float* gout, const int32_t* arg,
                         hipStream_t stream, bool s16, int* gw_tabs, const float* x0,
-                        const float* fshift, float* fold_partial, int K0) {
+                        const float* fshift, float* fold_partial, int K0, int blocks32) {
   using namespace fdma;
   const int64_t tiles = (max_rows + TR - 1) / TR;
   const int nr = rt.n < 1 ? 1 : rt.n;
+  if (K == 32 && N == 32) {
+    // the edge MLP's 32 -> 32 (and the 18 -> 32 layer folded under it): 4-wave workgroups on the
+    // grid of the register-staged <8, 2> launch (blocks32, the caller's), so that tiles, tables and
+    // statistics records fall to the same waves and every sum keeps its order
+    if (pooled || s16 || blocks32 < 1) return 0;
+    const dim3 grid((unsigned)blocks32, (unsigned)nr);
+    if (x0) {
+      if (!fmlp_dma_fold_supported(K0, K, N) || !lo || !fshift || !fold_partial || !pam) return 0;
+      bwd_dma_kernel<32, 32, 4, 4, true, false, false, 18><<<grid, 4 * 64, 0, stream>>>(
+          gy, h, 0, 0, am, sc, bs, slope, c1, c2, c3, xprev, pam, psc, pbs, pslope, W, nullptr,
+          gw_partial, pstat_partial, perm, pos_seg, gout, arg, rt, x0, fshift, fold_partial);
+    } else if (lo) {
+      bwd_dma_kernel<32, 32, 4, 4, true, false><<<grid, 4 * 64, 0, stream>>>(
+          gy, h, 0, 0, am, sc, bs, slope, c1, c2, c3, xprev, pam, psc, pbs, pslope, W, gx,
+          gw_partial, pstat_partial, perm, pos_seg, gout, arg, rt);
+    } else {
+      bwd_dma_kernel<32, 32, 4, 4, false, false><<<grid, 4 * 64, 0, stream>>>(
+          gy, h, 0, 0, am, sc, bs, slope, c1, c2, c3, xprev, pam, psc, pbs, pslope, W, gx,
+          gw_partial, pstat_partial, perm, pos_seg, gout, arg, rt);
+    }
+    if (gw_tabs) *gw_tabs = blocks32;
+    return blocks32 * 4;
+  }
   if (x0) {                                 // FOLD: the 12 -> 32 layer under 32 -> 64 (same grid)
     if (!fmlp_dma_fold_supported(K0, K, N) || pooled || s16 || !lo || !fshift || !fold_partial || !pam) return 0;
     int64_t blocks = (tiles + 8 - 1) / 8;
