@@ -972,6 +972,23 @@ int spt_skinny_dw_supported(int K, int N);
 size_t spt_skinny_dw_workspace_bytes(int K, int N);
 int spt_skinny_dw_f32(const float* gy, const float* x, int64_t rows, int N, int K, float* gw,
                       float* gb, void* ws, size_t ws_bytes, spt_stream_t stream);
+/* One-pass backward of y = x W^T + b for the attention blocks' Linears (K = 64, N in {64, 192}, the
+ * split-bf16 and bf16 matrix modes): ONE launch reads gy [rows, N] and x [rows, K] once and writes
+ * gx[rows,K] = gy W (bitwise spt_skinny_linear_wt_m_f32's), gw[N,K] = gy^T x_n and gb[N] (nullable)
+ * = column sums of gy; x_n = x through the pre-norm tables of spt_skinny_dw_pre_m_f32 (pre_am NULL
+ * = plain x; the instance given the tables is bitwise the plain one given the normalised rows).
+ * One [N x K | N] table per workgroup, summed in a fixed order (deterministic).
+ * ws: spt_skinny_linear_bwd_workspace_bytes(K, N) bytes of device scratch, checked before any launch.
+ * spt_skinny_bwd_fused: process switch the autograd wrappers consult (default on; the environment's
+ * SPT_SKINNY_BWD_FUSED=0 turns it off; < 0: query); returns the previous value. */
+int spt_skinny_linear_bwd_supported(int K, int N, int num_graphs, int mode);
+size_t spt_skinny_linear_bwd_workspace_bytes(int K, int N);
+int spt_skinny_linear_bwd_m_f32(const float* gy, const float* x, const float* W, int64_t rows, int N,
+                                int K, float* gx, float* gw, float* gb, const float* pre_am,
+                                const float* pre_scale, const float* pre_bias, const int64_t* batch,
+                                int num_graphs, int mode, void* ws, size_t ws_bytes,
+                                spt_stream_t stream);
+int spt_skinny_bwd_fused(int on);
 /* Narrow Linears (N <= 16 outputs: the classifier heads, src/nn/mlp.py:128-142).  Forward: the
  * skinny kernel above accepts N <= 16 with K in {32, 64, 128} (missing columns read as zero, not
  * stored).  Backward in ONE pass over x and gy for K = 64 and (round 5: the KITTI-360 width's heads,

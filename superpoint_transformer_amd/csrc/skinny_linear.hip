@@ -611,6 +611,223 @@ __global__ __launch_bounds__(1024) void sum_tables_kernel(const float* __restric
   }
 }
 
+// One-pass backward of y = x W^T + b for K = 64 inputs and NN = 64 / 192 outputs (the attention
+// blocks' out_proj / qkv): gx = gy W, gW = gy^T x_n and gb = column sums of gy from ONE read of gy
+// and x (the two-launch route reads gy twice, and x once per 64-column slab of gy).
+// An 8-wave workgroup strides 64-row macro-tiles.  Every element of gy and x is split ONCE, on its
+// way into LDS (x through the PRE map of skinny_dw_kernel<.., PRE> first, same fmaf): the tiles live
+// there as bf16 planes (hi | lo, split_planes' values), like W for the whole launch; the next
+// macro-tile's rows are requested into registers before the products.
+//   gx: wave w takes row tile w >> 1 and output blocks 2 (w & 1), + 1.  Every element's contraction
+//       is the one of skinny_linear_kernel / skinny_linear_wlds_kernel with a transposed weight:
+//       ascending 32-column steps of gy, mfma_planes<PR> per step - bitwise their output.
+//   gW: wave w owns k-blocks 2 (w & 1), + 1 of n-blocks (w >> 1) NN / 64 ..; the 64 rows are two
+//       contraction steps of v_mfma_f32_16x16x32_bf16, both operands read TRANSPOSED out of the
+//       row-major planes (ds_read_b64_tr_b16: lane group g takes rows 4 g .. 4 g + 3 and 16 + 4 g ..
+//       of the step, lane c of it column c; rows of NN + 16 / 80 values: conflict-free).  The
+//       workgroup's table [NN x 64] stays in accumulators for the launch and is written once;
+//       sum_tables_kernel adds the workgroup tables in a fixed order.
+//   gb: the unrounded values, summed per thread and staging slot (a slot's columns are the same in
+//       every macro-tile), then over the 64 rows of slots in order.
+// PRE and plain instances differ in the staging of x only.
+constexpr int BF_ROWS = 64;    // rows per macro-tile
+constexpr int BF_WAVES = 8;
+constexpr int BF_BLOCKS = 256; // workgroups (= partial tables) per resident round: NN = 192 one per CU, NN = 64 two
+__host__ __device__ constexpr int bf_per_cu(int NN) { return NN == 64 ? 2 : 1; }
+typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+// rows r0 .. r0 + 3 and r0 + 16 .. r0 + 19 of 16 columns of a row-major plane as an MFMA operand:
+// `at` = this lane's address for the first block (row r0 + ((lane >> 2) & 3), column 4 (lane & 3))
+__device__ __forceinline__ bf16x8 read_tr_operand(const __bf16* at, int ld) {
+  const bf16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)at);
+  const bf16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(at + 16 * ld));
+  return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+template <int NPL>
+__device__ __forceinline__ void split_planes4(const float4& v, bf16x4 (&p)[NPL]) {
+  const float x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const __bf16 a = (__bf16)x[i];
+    p[0][i] = a;
+    if constexpr (NPL >= 2) p[1][i] = (__bf16)(x[i] - (float)a);   // (the difference is exact)
+  }
+}
+template <int NN, bool PRE, int PR>
+__global__ __launch_bounds__(BF_WAVES * 64, 2 * bf_per_cu(NN)) void skinny_bwd_fused_kernel(
+    const float* __restrict__ gy, const float* __restrict__ x, const float* __restrict__ W, int64_t rows,
+    float* __restrict__ gx, float* __restrict__ partial, const float* __restrict__ pam,
+    const float* __restrict__ psc, const float* __restrict__ pbs, const int64_t* __restrict__ batch,
+    int PB) {
+  constexpr int K = 64, NT = BF_WAVES * 64, LDG = NN + 16, LDX = K + 16, LDW = NN + 8;
+  constexpr int NPL = skinny_planes(PR), KS = NN / 32, NBW = NN / 64;
+  constexpr int VG = BF_ROWS * NN / 4 / NT, VX = BF_ROWS * K / 4 / NT;   // float4 per thread per macro-tile
+  static_assert(NN % 64 == 0 && (PR == 1 || PR == 3), "whole 64-column slabs, a bf16 mode");
+  static_assert(BF_ROWS * NN / 4 % NT == 0 && BF_ROWS * K / 4 % NT == 0, "whole float4 rounds");
+  constexpr int GPL = NPL == 1 ? 2 : NPL;               // (two planes' room in every mode: the gb slots below)
+  static_assert(GPL * BF_ROWS * LDG * 2 >= BF_ROWS * NN * 4, "the gb slots fit the gy planes");
+  __shared__ __attribute__((aligned(16))) __bf16 g_pl[GPL * BF_ROWS * LDG];   // [plane][row][n]
+  __shared__ __attribute__((aligned(16))) __bf16 x_pl[NPL * BF_ROWS * LDX];   // [plane][row][k]
+  __shared__ __attribute__((aligned(16))) __bf16 w_pl[NPL * K * LDW];         // [plane][k][n]
+  __shared__ __attribute__((aligned(16))) float ptab[PRE ? 2 * PRE_MAX + K : 4];   // am | sc | bias
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int g = lane >> 4, c = lane & 15;
+
+  // W [NN][K] -> planes [k][n]: 8 values of a column of W per thread (coalesced along k)
+  for (int q = tid; q < K * (NN / 8); q += NT) {
+    const int k = q & (K - 1), n8 = q / K;
+    float wv[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) wv[j] = W[(size_t)(8 * n8 + j) * K + k];
+    bf16x8 pl[NPL];
+    split_planes<NPL>(wv, pl);
+#pragma unroll
+    for (int p = 0; p < NPL; ++p) *reinterpret_cast<bf16x8*>(w_pl + p * K * LDW + k * LDW + 8 * n8) = pl[p];
+  }
+  if constexpr (PRE) {
+    for (int i = tid; i < PB * K; i += NT) {
+      ptab[i] = pam[i];
+      ptab[PRE_MAX + i] = psc[i];
+    }
+    for (int i = tid; i < K; i += NT) ptab[2 * PRE_MAX + i] = pbs[i];
+  }
+
+  const int rt = wid >> 1, nh = wid & 1;                // gx: row tile, pair of output blocks
+  const int kp = wid & 1, nb0 = (wid >> 1) * NBW;       // gW: pair of k-blocks, first n-block
+  f32x4 CW[NBW][2];                                     // CW[i][kk][r] = gW[16 (nb0 + i) + 4 g + r][16 (2 kp + kk) + c]
+#pragma unroll
+  for (int i = 0; i < NBW; ++i) CW[i][0] = CW[i][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  float4 bs[VG];                                        // column sums of this thread's staging slots
+#pragma unroll
+  for (int v = 0; v < VG; ++v) bs[v] = make_float4(0.f, 0.f, 0.f, 0.f);
+
+  const int64_t ntiles = (rows + BF_ROWS - 1) / BF_ROWS;
+  float4 ng[VG], nx[VX];
+  int xg[VX];                                           // graph of the row each x chunk belongs to
+  auto fetch = [&](int64_t t) {                         // rows past the end read as zero
+    const int64_t gbase = t * BF_ROWS * (int64_t)NN, glim = rows * (int64_t)NN;
+#pragma unroll
+    for (int v = 0; v < VG; ++v) {                      // the gy tile is one contiguous run
+      const int64_t e = gbase + (int64_t)(v * NT + tid) * 4;
+      ng[v] = (e < glim) ? *reinterpret_cast<const float4*>(gy + e) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int v = 0; v < VX; ++v) {
+      const int q = v * NT + tid;
+      const int64_t row = t * BF_ROWS + q / (K / 4);
+      nx[v] = (row < rows) ? *reinterpret_cast<const float4*>(x + row * K + (q & (K / 4 - 1)) * 4)
+                           : make_float4(0.f, 0.f, 0.f, 0.f);
+      if constexpr (PRE) xg[v] = (row < rows) ? (batch ? (int)batch[row] : 0) : -1;
+    }
+  };
+  if ((int64_t)blockIdx.x < ntiles) fetch(blockIdx.x);
+  for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    __syncthreads();                                    // the previous tile's products are done (first round: W planes)
+#pragma unroll
+    for (int v = 0; v < VG; ++v) {
+      const int q4 = (v * NT + tid) * 4, rr = q4 / NN, col = q4 - rr * NN;
+      bs[v].x += ng[v].x; bs[v].y += ng[v].y; bs[v].z += ng[v].z; bs[v].w += ng[v].w;
+      bf16x4 pl[NPL];
+      split_planes4<NPL>(ng[v], pl);
+#pragma unroll
+      for (int p = 0; p < NPL; ++p) *reinterpret_cast<bf16x4*>(g_pl + p * BF_ROWS * LDG + rr * LDG + col) = pl[p];
+    }
+#pragma unroll
+    for (int v = 0; v < VX; ++v) {
+      const int q = v * NT + tid, rr = q / (K / 4), ch = q & (K / 4 - 1);
+      float4 w = nx[v];
+      if constexpr (PRE) {
+        if (xg[v] >= 0) {                               // rows past the end stay zero
+          const float4 a = *reinterpret_cast<const float4*>(ptab + xg[v] * K + ch * 4);
+          const float4 sc4 = *reinterpret_cast<const float4*>(ptab + PRE_MAX + xg[v] * K + ch * 4);
+          const float4 b4 = *reinterpret_cast<const float4*>(ptab + 2 * PRE_MAX + ch * 4);
+          w.x = fmaf(w.x - a.x, sc4.x, b4.x); w.y = fmaf(w.y - a.y, sc4.y, b4.y);
+          w.z = fmaf(w.z - a.z, sc4.z, b4.z); w.w = fmaf(w.w - a.w, sc4.w, b4.w);
+        }
+      }
+      bf16x4 pl[NPL];
+      split_planes4<NPL>(w, pl);
+#pragma unroll
+      for (int p = 0; p < NPL; ++p) *reinterpret_cast<bf16x4*>(x_pl + p * BF_ROWS * LDX + rr * LDX + ch * 4) = pl[p];
+    }
+    __syncthreads();
+    if (t + gridDim.x < ntiles) fetch(t + gridDim.x);   // in flight during the products
+
+    // gx rows 16 rt .. of the macro-tile, columns 32 nh ..
+    {
+      f32x4 C[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
+      const __bf16* al = g_pl + (16 * rt + c) * LDG + 8 * g;
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        bf16x8 Ap[NPL];
+#pragma unroll
+        for (int p = 0; p < NPL; ++p) Ap[p] = *reinterpret_cast<const bf16x8*>(al + p * BF_ROWS * LDG + 32 * ks);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          bf16x8 Bp[NPL];
+#pragma unroll
+          for (int p = 0; p < NPL; ++p)
+            Bp[p] = *reinterpret_cast<const bf16x8*>(w_pl + p * K * LDW + (16 * (2 * nh + i) + c) * LDW +
+                                                     32 * ks + 8 * g);
+          C[i] = mfma_planes<PR>(Ap, Bp, C[i]);
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int64_t row = t * BF_ROWS + 16 * rt + 4 * g + r;
+        if (row < rows) {
+#pragma unroll
+          for (int i = 0; i < 2; ++i)
+            __builtin_nontemporal_store(C[i][r], gx + row * K + 16 * (2 * nh + i) + c);
+        }
+      }
+    }
+
+    // gW: two contraction steps of 32 rows, operands transposed on their way out of LDS
+#pragma unroll
+    for (int s = 0; s < BF_ROWS / 32; ++s) {
+      const int r0 = 32 * s + 4 * g + ((lane >> 2) & 3), c0 = 4 * (lane & 3);
+      bf16x8 Ap[NBW][NPL];
+#pragma unroll
+      for (int i = 0; i < NBW; ++i)
+#pragma unroll
+        for (int p = 0; p < NPL; ++p)
+          Ap[i][p] = read_tr_operand(g_pl + p * BF_ROWS * LDG + r0 * LDG + 16 * (nb0 + i) + c0, LDG);
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        bf16x8 Bp[NPL];
+#pragma unroll
+        for (int p = 0; p < NPL; ++p)
+          Bp[p] = read_tr_operand(x_pl + p * BF_ROWS * LDX + r0 * LDX + 16 * (2 * kp + kk) + c0, LDX);
+#pragma unroll
+        for (int i = 0; i < NBW; ++i) CW[i][kk] = mfma_planes<PR>(Ap[i], Bp, CW[i][kk]);
+      }
+    }
+  }
+
+  // partial[workgroup][NN x K | NN]
+  float* pw = partial + (size_t)blockIdx.x * ((size_t)NN * K + NN);
+#pragma unroll
+  for (int i = 0; i < NBW; ++i)
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        pw[(size_t)(16 * (nb0 + i) + 4 * g + r) * K + 16 * (2 * kp + kk) + c] = CW[i][kk][r];
+  // gb: slot (tid, v) holds columns of element 4 (v NT + tid) of the [64 x NN] tile
+  __syncthreads();
+  float* slots = reinterpret_cast<float*>(g_pl);
+#pragma unroll
+  for (int v = 0; v < VG; ++v) *reinterpret_cast<float4*>(slots + (v * NT + tid) * 4) = bs[v];
+  __syncthreads();
+  if (tid < NN) {
+    float v = 0.f;
+    for (int rr = 0; rr < BF_ROWS; ++rr) v += slots[rr * NN + tid];
+    pw[(size_t)NN * K + tid] = v;
+  }
+}
+
 // Backward of a NARROW Linear (N <= 16 outputs, K = 64 inputs: the classifier heads, src/nn/mlp.py:
 // 128-142) in one pass over x and gy: lane = input column k.  Per row the N gradient values are
 // wave-uniform (read out of a register tile with v_readlane), so dX[row, k] = sum_n g_n W[n, k]
@@ -947,6 +1164,61 @@ static int skinny_linear_impl(const float* x, int64_t rows, int K, const float* 
       break;
     }
   }
+  SPT_CHECK_LAUNCH();
+  return 0;
+}
+
+// One-pass backward (skinny_bwd_fused_kernel): gx[rows, K] = gy W, gw[N, K] = gy^T x_n, gb[N] = column
+// sums of gy (nullable) from one read of gy [rows, N] and x [rows, K].  K = 64, N in {64, 192}, the
+// bf16 matrix modes (split bf16 and bf16); pre_am .. as in spt_skinny_dw_pre_m_f32.  gx is bitwise
+// spt_skinny_linear_wt_m_f32's; gw / gb sum one table per workgroup in a fixed order.
+static std::atomic<int> g_bwd_fused{[] { const char* e = getenv("SPT_SKINNY_BWD_FUSED"); return (e && atoi(e) == 0) ? 0 : 1; }()};
+extern "C" int spt_skinny_bwd_fused(int on) {
+  const int prev = g_bwd_fused;
+  if (on >= 0) g_bwd_fused = on ? 1 : 0;
+  return prev;
+}
+extern "C" int spt_skinny_linear_bwd_supported(int K, int N, int num_graphs, int mode) {
+  return K == 64 && (N == 64 || N == 192) && skinny_pr_bwd(mode) != 0 && num_graphs >= 1 &&
+         num_graphs * K <= PRE_MAX;
+}
+extern "C" size_t spt_skinny_linear_bwd_workspace_bytes(int K, int N) {
+  return (size_t)BF_BLOCKS * bf_per_cu(N) * N * (K + 1) * sizeof(float);
+}
+extern "C" int spt_skinny_linear_bwd_m_f32(const float* gy, const float* x, const float* W, int64_t rows,
+                                           int N, int K, float* gx, float* gw, float* gb,
+                                           const float* pre_am, const float* pre_scale,
+                                           const float* pre_bias, const int64_t* batch, int num_graphs,
+                                           int mode, void* ws, size_t ws_bytes, spt_stream_t stream_) {
+  const int pr = skinny_pr_bwd(mode);
+  hipStream_t stream = (hipStream_t)stream_;
+  SPT_CHECK_ARG(rows >= 0, "bad shape");
+  const bool pre = pre_am != nullptr;
+  SPT_CHECK_ARG(spt_skinny_linear_bwd_supported(K, N, pre ? num_graphs : 1, mode),
+                "(K, N) not built, the f32-exact mode or num_graphs * K too large");
+  SPT_CHECK_ARG(!pre || (pre_scale && pre_bias), "pre-normalisation: incomplete tables");
+  SPT_CHECK_ARG(gw && (rows == 0 || (gy && x && W && gx)), "null pointer");
+  SPT_CHECK_ARG(ws && ws_bytes >= spt_skinny_linear_bwd_workspace_bytes(K, N), "workspace too small");
+  if (rows == 0) {
+    hipMemsetAsync(gw, 0, (size_t)N * K * sizeof(float), stream);
+    if (gb) hipMemsetAsync(gb, 0, (size_t)N * sizeof(float), stream);
+    return 0;
+  }
+  int64_t bx = ceil_div(rows, (int64_t)BF_ROWS);
+  if (bx > BF_BLOCKS * bf_per_cu(N)) bx = BF_BLOCKS * bf_per_cu(N);
+  float* partial = (float*)ws;
+#define SPT_BF(NN_, PRE_, PR_)                                                                      \
+  skinny_bwd_fused_kernel<NN_, PRE_, PR_><<<(unsigned)bx, BF_WAVES * 64, 0, stream>>>(               \
+      gy, x, W, rows, gx, partial, pre_am, pre_scale, pre_bias, batch, num_graphs);
+#define SPT_BFS(NN_, PRE_) if (pr == 3) { SPT_BF(NN_, PRE_, 3) } else { SPT_BF(NN_, PRE_, 1) }
+  if (N == 192) {
+    if (pre) { SPT_BFS(192, true) } else { SPT_BFS(192, false) }
+  } else {
+    if (pre) { SPT_BFS(64, true) } else { SPT_BFS(64, false) }
+  }
+#undef SPT_BFS
+#undef SPT_BF
+  sum_tables_kernel<<<(N * (K + 1) + 15) / 16, 1024, 0, stream>>>(partial, (int)bx, N * (K + 1), N * K, gw, gb);
   SPT_CHECK_LAUNCH();
   return 0;
 }

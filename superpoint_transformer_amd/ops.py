@@ -1011,11 +1011,59 @@ def _skinny_dw(g, x, want_bias=False, mode=-1):
     return (gw, gb) if want_bias else gw
 
 
+_BWD_ROUTE = {"fused": 0, "split": 0}
+
+
+def skinny_bwd_fused(on=None):
+    """Switch of the one-pass backward of the attention blocks' Linears (dX, dW and db from one read
+    of the gradient, csrc/skinny_linear.hip: ``spt_skinny_linear_bwd_m_f32``); default on,
+    ``SPT_SKINNY_BWD_FUSED=0`` in the environment turns it off.  Returns the previous setting."""
+    return bool(_lib.lib.spt_skinny_bwd_fused(-1 if on is None else int(bool(on))))
+
+
+def skinny_bwd_route_counts():
+    """Calls of the tall Linears' backward so far that took the one-pass entry (``fused``) and the
+    dX / dW launches (``split``) - the route query of the tests."""
+    return dict(_BWD_ROUTE)
+
+
+def _skinny_bwd_ok(g, x, weight, num_graphs, mode):
+    return bool(x.is_cuda and x.dtype == torch.float32 and g.dtype == torch.float32
+                and weight.dtype == torch.float32 and x.dim() == 2 and x.shape[0] >= _SKINNY_MIN_ROWS
+                and _lib.lib.spt_skinny_bwd_fused(-1)
+                and _lib.lib.spt_skinny_linear_bwd_supported(x.shape[1], g.shape[1], int(num_graphs),
+                                                             int(mode)))
+
+
+def _skinny_bwd(g, x, weight, want_bias, mode, pre=None):
+    """(gx, gw, gb) of y = x W^T + b from one pass over (g, x); ``pre`` = (am, scale, bias, batch, B):
+    x normalised on its way in (the folded pre-norm), gx then is the gradient of the normalised rows."""
+    g, x, w = g.contiguous(), x.detach().contiguous(), weight.detach().contiguous()
+    rows, k = x.shape
+    n = g.shape[1]
+    dev = x.device
+    gx = torch.empty((rows, k), dtype=torch.float32, device=dev)
+    gw = torch.empty((n, k), dtype=torch.float32, device=dev)
+    gb = torch.empty(n, dtype=torch.float32, device=dev) if want_bias else None
+    am, sc, pb, batch, B = pre if pre is not None else (None, None, None, None, 1)
+    ws = _workspace(_lib.lib.spt_skinny_linear_bwd_workspace_bytes(k, n), dev)
+    with torch.cuda.device(dev):
+        st = _lib.lib.spt_skinny_linear_bwd_m_f32(
+            _lib.ptr(g), _lib.ptr(x), _lib.ptr(w), rows, n, k, _lib.ptr(gx), _lib.ptr(gw), _lib.ptr(gb),
+            _lib.ptr(am), _lib.ptr(sc), _lib.ptr(pb), _lib.ptr(batch), int(B), int(mode), _lib.ptr(ws),
+            ws.numel(), _lib.stream_ptr(dev))
+    _lib.check(st, "spt_skinny_linear_bwd_m_f32")
+    _BWD_ROUTE["fused"] += 1
+    return gx, gw, gb
+
+
 class _TallLinear(torch.autograd.Function):
     """y = x W^T (+ b) for [rows >> features] operands.  Forward and dX run on the
     hand-written skinny-GEMM kernel when the shape is built (K in {32,64,128,192},
     N % 64 == 0 - the attention block's qkv / out_proj), else on the library; dW on the
-    skinny dW kernel (K in {32, 64}) or a batched library GEMM over row chunks."""
+    skinny dW kernel (K in {32, 64}) or a batched library GEMM over row chunks.  Where both dX and
+    dW are wanted and the one-pass backward is built (K = 64, N in {64, 192}, a bf16 matrix mode,
+    ``skinny_bwd_fused``) one launch reads the gradient once for dX, dW and db."""
 
     @staticmethod
     def forward(ctx, x, weight, bias):
@@ -1052,10 +1100,13 @@ class _TallLinear(torch.autograd.Function):
             return gx, gw, gb
         gx = None
         smode = getattr(ctx, "smode", -1)
+        want_gb = ctx.has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and _skinny_bwd_ok(g, x, weight, 1, smode):
+            return _skinny_bwd(g, x, weight, want_gb, smode)
+        _BWD_ROUTE["split"] += 1
         if ctx.needs_input_grad[0]:
             gx = _input_grad(g, weight, smode)
         gw = gb = None
-        want_gb = ctx.has_bias and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1]:
             if _skinny_dw_ok(g, x):
                 gw = _skinny_dw(g, x, want_gb, smode)
@@ -1195,18 +1246,24 @@ class _NormLinear(torch.autograd.Function):
         n = wd.shape[0]
         dev = xd.device
         gy = gy.contiguous()
-        # gradient wrt the normalised rows: dX of the Linear
-        gxn = _input_grad(gy, wd, ctx.smode)
-        # weight / bias gradient against the rows normalised on the fly
-        gw = torch.empty((n, d), dtype=torch.float32, device=dev)
-        gb = torch.empty(n, dtype=torch.float32, device=dev) if has_bias else None
-        ws = _workspace(_lib.lib.spt_skinny_dw_workspace_bytes(d, n), dev)
-        with torch.cuda.device(dev):
-            st = _lib.lib.spt_skinny_dw_pre_m_f32(
-                _lib.ptr(gy), _lib.ptr(xd), rows, n, d, _lib.ptr(gw), _lib.ptr(gb), _lib.ptr(am),
-                _lib.ptr(sc), _lib.ptr(b), _lib.ptr(batch), B, ctx.smode, _lib.ptr(ws), ws.numel(),
-                _lib.stream_ptr(dev))
-        _lib.check(st, "spt_skinny_dw_pre_m_f32")
+        if ctx.needs_input_grad[7] and _skinny_bwd_ok(gy, xd, wd, B, ctx.smode):
+            # gradient wrt the normalised rows, weight / bias gradient against the rows normalised
+            # on the fly: one pass over (gy, x)
+            gxn, gw, gb = _skinny_bwd(gy, xd, wd, has_bias, ctx.smode, (am, sc, b, batch, B))
+        else:
+            _BWD_ROUTE["split"] += 1
+            # gradient wrt the normalised rows: dX of the Linear
+            gxn = _input_grad(gy, wd, ctx.smode)
+            # weight / bias gradient against the rows normalised on the fly
+            gw = torch.empty((n, d), dtype=torch.float32, device=dev)
+            gb = torch.empty(n, dtype=torch.float32, device=dev) if has_bias else None
+            ws = _workspace(_lib.lib.spt_skinny_dw_workspace_bytes(d, n), dev)
+            with torch.cuda.device(dev):
+                st = _lib.lib.spt_skinny_dw_pre_m_f32(
+                    _lib.ptr(gy), _lib.ptr(xd), rows, n, d, _lib.ptr(gw), _lib.ptr(gb), _lib.ptr(am),
+                    _lib.ptr(sc), _lib.ptr(b), _lib.ptr(batch), B, ctx.smode, _lib.ptr(ws), ws.numel(),
+                    _lib.stream_ptr(dev))
+            _lib.check(st, "spt_skinny_dw_pre_m_f32")
         # the norm's backward, with the residual branch's gradient added in its apply pass
         gx = torch.empty_like(xd)
         g_w, g_b, g_a = (torch.empty(d, dtype=torch.float32, device=dev) for _ in range(3))
