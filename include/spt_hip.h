@@ -1353,6 +1353,58 @@ int spt_hist_loss_bwd_f32(const float* logits, const int64_t* target, int64_t ro
 int spt_confusion_matrix_i64(const int64_t* pred, const int64_t* target, int64_t rows, int C,
                              int ncols, int64_t* confmat, spt_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Augmentations of the per-batch training chain              (csrc/augment.hip)
+ * NAGJitterKey, NAGDropoutColumns, NAGDropoutRows (src/transforms/data.py:440-721),
+ * RandomTiltAndRotate, RandomAnisotropicScale, RandomAxisFlip (src/transforms/geometry.py:
+ * 28-245), NAGColorAutoContrast, NAGColorDrop (src/transforms/point.py:374-545).
+ *
+ * Every entry: f32; element (i, c) of a tensor at p[i * ld + c] (ld = column count for a tensor
+ * of its own, ld = F and p = x + column for a block of a wider [n, F] table); out may equal the
+ * input; n = 0 returns 0 without a launch; no host read.  The values depend on (seed, logical
+ * index) only, never on ld, alignment or grid size.
+ *
+ * Random stream: r = rand32(seed, counter), the splitmix64 finaliser of the sampler, with the
+ * counter of an element its logical index i * n_cols + c and the counter of a row decision i.
+ *   decision: u = (r >> 8) * 2^-24 in [0, 1), taken when u < p (f32 compare).
+ *   noise:    u = ((r >> 8) + 0.5) * 2^-24 in (0, 1),
+ *             clamp(sigma * sqrt(2) * erfinv(lo + u * (hi - lo)), -trunc, trunc)
+ *             with lo = 2 Phi(-trunc / sigma) - 1 and hi = 2 Phi(trunc / sigma) - 1 from the
+ *             caller (torch.nn.init.trunc_normal_); trunc <= 0: lo = -1, hi = 1 and no clamp
+ *             (the tail then ends at 5.42 sigma).  Always finite.
+ *
+ * spt_augment_features_f32: flags bit 0 x += noise(seed_jitter), bit 1 zero the columns whose
+ *   bit is set in col_mask (n_cols <= 64), bit 2 zero the rows with u(seed_rows, i) < p_rows,
+ *   in this order.
+ * spt_augment_geometry_f32: mode 0 pos [n, 3], 1 normal [n, 3], 2 edge_attr [n, 7].  flags bit 0
+ *   jitter (pos only), bit 1 rotate v <- v R^T (rotation: 9 HOST floats, row major), bit 2
+ *   scale (scale: 3 HOST floats; normal: then v / max(||v||, 1e-12); edge: columns 3..6 times
+ *   scale_norm), bit 3 negate column flip_axis.  normal: rows with z < 0 are negated after the
+ *   rotation and after the flip.  Steps run in bit order; the fused call is bit-identical to the
+ *   same steps in separate calls (fixed fma order: csrc/augment.hip).
+ * spt_augment_color_range_f32: range6 <- {min of columns 0..2, max of columns 0..2} of the
+ *   (jittered, when jitter != 0) colours [n, 3]; integer atomics, bitwise reproducible; a NaN
+ *   in a column makes its two records NaN.
+ * spt_augment_color_f32: flags bit 0 jitter, bit 1 auto-contrast
+ *   one_minus_blend * c + blend * ((c - lo) / (hi - lo)) with lo / hi from range6 (computed
+ *   with the same seed), IEEE division, bit 2 c * 0.
+ * ---------------------------------------------------------------------- */
+int spt_augment_features_f32(const float* x, float* out, int64_t n, int n_cols, int64_t ld_x,
+                             int64_t ld_out, int flags, uint64_t seed_jitter, double sigma,
+                             double trunc, double lo, double hi, uint64_t col_mask,
+                             uint64_t seed_rows, float p_rows, spt_stream_t stream);
+int spt_augment_geometry_f32(const float* x, float* out, int64_t n, int64_t ld_x, int64_t ld_out,
+                             int mode, int flags, uint64_t seed_jitter, double sigma, double trunc,
+                             double lo, double hi, const float* rotation, const float* scale,
+                             float scale_norm, int flip_axis, spt_stream_t stream);
+int spt_augment_color_range_f32(const float* color, int64_t n, int64_t ld, int jitter,
+                                uint64_t seed, double sigma, double trunc, double lo, double hi,
+                                float* range6, spt_stream_t stream);
+int spt_augment_color_f32(const float* color, float* out, int64_t n, int64_t ld_color,
+                          int64_t ld_out, int flags, uint64_t seed, double sigma, double trunc,
+                          double lo, double hi, const float* range6, float blend,
+                          float one_minus_blend, spt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -250,6 +250,14 @@ SIGNATURES = {
     "spt_point_color_workspace_bytes": (_sz, [_i64]),
     "spt_point_color_f32": (_int, [_p, _int, _i64, _int, _p, _i64, _p, _i64, _p, _i64, _p, _sz, _p]),
     "spt_point_density_f32": (_int, [_p, _i64, _p, _i64, _i64, _int, _p, _p]),
+    "spt_augment_features_f32": (_int, [_p, _p, _i64, _int, _i64, _i64, _int, _c.c_uint64, _f64, _f64,
+                                        _f64, _f64, _c.c_uint64, _c.c_uint64, _f32, _p]),
+    "spt_augment_geometry_f32": (_int, [_p, _p, _i64, _i64, _i64, _int, _int, _c.c_uint64, _f64, _f64,
+                                        _f64, _f64, _p, _p, _f32, _int, _p]),
+    "spt_augment_color_range_f32": (_int, [_p, _i64, _i64, _int, _c.c_uint64, _f64, _f64, _f64, _f64,
+                                           _p, _p]),
+    "spt_augment_color_f32": (_int, [_p, _p, _i64, _i64, _i64, _int, _c.c_uint64, _f64, _f64, _f64,
+                                     _f64, _p, _f32, _f32, _p]),
 }
 
 

@@ -19,18 +19,10 @@
 // the counts / pointers (exact) and on the sampling contract (members of the right
 // segment, distinct, kept by the mask, uniform) - see tests/test_sampling_gpu.py.
 #include "radix_sort.hpp"
+#include "rng.hpp"   // rand32(seed, counter)
 
 namespace spt {
 namespace sampling {
-
-// splitmix64 finaliser over (seed, counter): counter-based, no state, reproducible
-__device__ __forceinline__ uint32_t rand32(uint64_t seed, uint64_t i) {
-  uint64_t z = seed + 0x9E3779B97F4A7C15ull * (i + 1);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z = z ^ (z >> 31);
-  return (uint32_t)(z >> 32);
-}
 
 __global__ void random_keys_kernel(uint64_t seed, int64_t n, uint32_t* __restrict__ keys) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;

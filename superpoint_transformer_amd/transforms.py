@@ -11,7 +11,10 @@ __all__ = ["horizontal_edge_features", "EDGE_FEATURE_COLUMNS", "NodeSize", "Samp
            "SampleSegments", "SampleEdges", "OnTheFlyHorizontalEdgeFeatures",
            "SampleRadiusSubgraphs", "OnTheFlyInstanceGraph", "segment_sampling_weights",
            "NAGRestrictSize", "MortonOrder", "morton_code", "PartitionAdjacency", "GroundElevation",
-           "PointFeatures", "AddKeysTo"]
+           "PointFeatures", "AddKeysTo", "NAGJitterKey", "RandomTiltAndRotate",
+           "RandomAnisotropicScale", "RandomAxisFlip", "NAGDropoutColumns", "NAGDropoutRows",
+           "NAGColorAutoContrast", "NAGColorDrop", "GeometricAugmentation", "FeatureAugmentation",
+           "ColorAugmentation"]
 
 EDGE_FEATURE_COLUMNS = [
     "mean_off_x", "mean_off_y", "mean_off_z", "std_off_x", "std_off_y", "std_off_z",
@@ -580,3 +583,492 @@ class MortonOrder:
         back = torch.empty_like(out)
         back[origin] = out
         return back
+
+
+# ---------------------------------------------------------------------------
+# Augmentations of the training chain (configs/datamodule/semantic/default.yaml:250-264 and
+# 292-358), kernels in csrc/augment.hip, wrappers in augment.py.
+#
+# Every class is the reference's class of that name with its constructor signature, split in
+#   draw(nag)  -> params   host only: torch's CPU generator, in the order each docstring gives
+#   apply(nag, params)     no host read of device memory
+# and __call__ = apply(nag, draw(nag)).  A scalar decision (rotation, scale, flip, dropped
+# columns, contrast, blend, drop) is a host value in `params`; a per-element or per-row draw is
+# a 64-bit seed (segment._draw_seed: one torch.randint on the CPU generator) of the counter-based
+# generator, so torch.manual_seed makes a chain reproducible.
+# ---------------------------------------------------------------------------
+_NORMAL_KEYS = ("normal", "mean_normal")
+
+
+def _f32(t, what):
+    if t.dtype != torch.float32:
+        raise TypeError(f"{what} must be float32 (run NAGCast first), got {t.dtype}")
+    return t
+
+
+def _as_level_list(v, num_levels):
+    return list(v) if isinstance(v, list) else [v] * num_levels
+
+
+def _geometry_apply(nag, jitter=None, tilt=None, scale=None, flip=None):
+    """The geometric steps that are not None / skipped, fused: one launch per tensor touched.
+    ``jitter`` = {level: (sigma, trunc, seed)} of ``pos``, ``tilt`` = {'skip', 'R'}, ``scale`` =
+    {'scale'}, ``flip`` = {'flip', 'axis'}."""
+    from . import augment as A
+    R = None if tilt is None or tilt["skip"] else tilt["R"]
+    s = None if scale is None else scale["scale"]
+    axis = None if flip is None or not flip["flip"] else flip["axis"]
+    for i in range(nag.num_levels):
+        d = nag[i]
+        jit = None if jitter is None else jitter.get(i)
+        if d.pos is not None and (jit is not None or R is not None or s is not None
+                                  or axis is not None):
+            A.geometry_(_f32(d.pos, "pos"), A.POS, jitter=jit, R=R, scale=s, flip_axis=axis)
+        if R is None and s is None and axis is None:
+            continue
+        for k in _NORMAL_KEYS:
+            t = d.get(k)
+            if t is not None:
+                A.geometry_(_f32(t, k), A.NORMAL, R=R, scale=s, flip_axis=axis)
+        ea = d.edge_attr
+        if ea is not None:
+            assert ea.shape[1] == 7, \
+                "Expected exactly 7 features in `edge_attr`, generated with " \
+                "`_minimalistic_horizontal_edge_features`"
+            A.geometry_(_f32(ea, "edge_attr"), A.EDGE7, R=R, scale=s, flip_axis=axis)
+    return nag
+
+
+class NAGJitterKey:
+    """``NAGJitterKey`` (src/transforms/data.py:651-721): ``nag[i][key] += noise`` in place, noise
+    from the truncated normal of ``torch.nn.init.trunc_normal_(std=sigma, a=-trunc, b=trunc)``
+    (``trunc <= 0``: untruncated; one generator here, its tail ends at 5.42 sigma - see
+    ``augment``).  ``sigma`` / ``trunc`` may be per-level lists; ``sigma <= 0`` skips the level; a
+    missing key is skipped, or raises ``ValueError`` when ``strict``.
+
+    ``draw``: one ``segment._draw_seed()`` per (level, key) that is jittered, levels in order,
+    keys in order inside a level."""
+
+    def __init__(self, key=None, sigma=0.01, trunc=0.05, strict=False):
+        assert key is not None, "A key or list of keys must be specified"
+        assert isinstance(sigma, (int, float, list))
+        assert isinstance(trunc, (int, float, list))
+        self.key = [key] if isinstance(key, str) else list(key)
+        self.sigma, self.trunc, self.strict = sigma, trunc, strict
+
+    def draw(self, nag):
+        from .segment import _draw_seed
+        L = nag.num_levels
+        sigma, trunc = _as_level_list(self.sigma, L), _as_level_list(self.trunc, L)
+        params = {}
+        for i in range(L):
+            if sigma[i] <= 0:
+                continue
+            for k in self.key:
+                if nag[i].get(k) is None:
+                    if self.strict:
+                        raise ValueError(f"Input data does not have any '{k} attribute")
+                    continue
+                params[(i, k)] = (float(sigma[i]), float(trunc[i]), _draw_seed())
+        return params
+
+    def apply(self, nag, params):
+        from . import augment as A
+        for (i, k), (sigma, trunc, seed) in params.items():
+            A.jitter_(_f32(nag[i][k], k), sigma, trunc, seed=seed)
+        return nag
+
+    def __call__(self, nag):
+        return self.apply(nag, self.draw(nag))
+
+
+class RandomTiltAndRotate:
+    """``RandomTiltAndRotate`` (src/transforms/geometry.py:28-115): rotates ``pos``, ``normal``,
+    ``mean_normal`` (rows with z < 0 negated afterwards) and columns 0:3 of a 7-column
+    ``edge_attr`` (another width raises ``AssertionError``) of every level by ONE random matrix.
+
+    What the reference does, where it differs from its docstring: the axis offset is
+    ``MultivariateNormal(0, eye(2) * sigma)`` whose second positional argument is the COVARIANCE
+    (geometry.py:66-69), so the per-axis standard deviation is ``sqrt(sigma)`` with
+    ``sigma = phi / 180 * pi / 3``; ``phi == 0`` skips every level whatever ``theta`` is
+    (geometry.py:86-87).  ``R`` is ``rodrigues_rotation_matrix`` (src/utils/geometry.py:27-39)
+    evaluated on the host in f32 with the same torch operations.
+
+    ``draw``: the ``MultivariateNormal.sample()`` of two values (only when ``phi > 0``), then
+    ``torch.rand(1)`` for the angle (always, as the reference)."""
+
+    def __init__(self, phi=5, theta=180):
+        assert isinstance(phi, (int, float))
+        assert isinstance(theta, (int, float))
+        self.phi, self.theta = float(abs(phi)), float(abs(theta))
+
+    @staticmethod
+    def rotation_matrix(axis, theta_degrees):
+        """``rodrigues_rotation_matrix`` on host f32 tensors, operation for operation."""
+        import numpy as np
+        axis = axis / axis.norm()
+        k = axis
+        K = torch.tensor([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+        t = torch.tensor([theta_degrees / 180. * np.pi])
+        return torch.eye(3) + torch.sin(t) * K + (1 - torch.cos(t)) * K.mm(K)
+
+    def draw(self, nag=None):
+        sigma = self.phi / 180. * torch.pi / 3
+        if sigma > 0:
+            dist = torch.distributions.MultivariateNormal(torch.zeros(2), torch.eye(2) * sigma)
+            axis = torch.cat((dist.sample(), torch.ones(1)))
+            axis /= axis.norm()
+        else:
+            axis = torch.zeros(3, dtype=torch.float)
+            axis[2] = 1
+        theta = torch.rand(1) * 2 * self.theta - self.theta
+        return {"skip": sigma <= 0, "R": self.rotation_matrix(axis, theta)}
+
+    def apply(self, nag, params):
+        return _geometry_apply(nag, tilt=params)
+
+    def __call__(self, nag):
+        return self.apply(nag, self.draw(nag))
+
+
+class RandomAnisotropicScale:
+    """``RandomAnisotropicScale`` (src/transforms/geometry.py:118-186): ``pos * scale``, normals
+    ``F.normalize(normal * scale)``, ``edge_attr[:, :3] * scale`` and ``edge_attr[:, 3:] *
+    ||scale||_2`` (7 columns, another width raises).  Despite the name ONE uniform draw is shared
+    by the three axes: ``scale = 1 + (torch.rand(1) * 2 * delta - delta)`` (geometry.py:159), so
+    the axes differ only when ``delta`` is a 3-list.
+
+    ``draw``: ``torch.rand(1)``."""
+
+    def __init__(self, delta=0.2):
+        assert isinstance(delta, (float, int)) or isinstance(delta, (tuple, list))
+        if isinstance(delta, (float, int)):
+            delta = [float(delta)] * 3
+        assert len(delta) == 3
+        self.delta = torch.tensor(delta).abs().view(1, -1)
+
+    def draw(self, nag=None):
+        scale = 1 + (torch.rand(1) * 2 * self.delta - self.delta)
+        return {"scale": scale.view(3).float()}
+
+    def apply(self, nag, params):
+        return _geometry_apply(nag, scale=params)
+
+    def __call__(self, nag):
+        return self.apply(nag, self.draw(nag))
+
+
+class RandomAxisFlip:
+    """``RandomAxisFlip`` (src/transforms/geometry.py:189-245): negates column ``axis`` of
+    ``pos``, of the normals (rows with z < 0 negated afterwards) and of a 7-column ``edge_attr``.
+    The flip happens when the draw is ``<= p``: the reference returns early on ``rand > p``
+    (geometry.py:215).
+
+    ``draw``: ``torch.rand(1)``."""
+
+    def __init__(self, axis=0, p=0.5):
+        assert isinstance(axis, int)
+        assert isinstance(p, float)
+        self.axis, self.p = axis, p
+
+    def draw(self, nag=None):
+        return {"flip": not bool(torch.rand(1) > self.p), "axis": self.axis}
+
+    def apply(self, nag, params):
+        return _geometry_apply(nag, flip=params)
+
+    def __call__(self, nag):
+        return self.apply(nag, self.draw(nag))
+
+
+def _dropout_apply(nag, columns=None, rows=None, jitter=None, inplace=True, to_mean=False):
+    """Jitter, column dropout and row dropout of every (level, key) named by the three parameter
+    dicts, one launch per tensor.  ``to_mean`` takes a torch composition (no host read)."""
+    from . import augment as A
+    columns, rows, jitter = columns or {}, rows or {}, jitter or {}
+    for lk in list(dict.fromkeys(list(jitter) + list(columns) + list(rows))):
+        i, k = lk
+        a = _f32(nag[i][k], k)
+        mask = columns.get(lk)
+        row = rows.get(lk)
+        if to_mean:
+            if lk in jitter:
+                A.jitter_(a, *jitter[lk][:2], seed=jitter[lk][2])
+            out = a if inplace else a.clone()
+            mean = a.mean(dim=0)
+            if mask is not None:
+                sel = torch.tensor([(mask >> j) & 1 == 1 for j in range(mean.numel())],
+                                   device=a.device)
+                out = torch.where(sel.view(1, -1) if a.dim() == 2 else sel, mean, out)
+            if row is not None:
+                n = a.shape[0]
+                sel = A.unit(row[1], torch.arange(n, device=a.device)) < \
+                    torch.tensor(row[0], dtype=torch.float32, device=a.device)
+                out = torch.where(sel.view(-1, *([1] * (a.dim() - 1))), mean, out)
+            if inplace:
+                a.copy_(out)
+            else:
+                nag[i][k] = out
+            continue
+        out = None if inplace else torch.empty_like(a)
+        A.features_(a, jitter=jitter.get(lk), col_mask=mask,
+                    p_rows=None if row is None else row[0],
+                    seed_rows=None if row is None else row[1], out=out)
+        if out is not None:
+            nag[i][k] = out
+    return nag
+
+
+class NAGDropoutColumns:
+    """``NAGDropoutColumns`` (src/transforms/data.py:440-543, src/utils/dropout.py:7-22): every
+    column of ``nag[i][key]`` is zeroed (set to its mean with ``to_mean``) with probability
+    ``p``.  ``p <= 0`` does nothing.  At a level, the first MISSING key ends that level - the
+    early ``return`` of ``DropoutColumns._process`` (data.py:470-472).  ``inplace=False`` writes a
+    new tensor.
+
+    ``draw``: ``torch.rand(n_cols) < p`` per (level, key), levels in order, keys in order."""
+
+    def __init__(self, level="all", p=0.5, key=None, inplace=False, to_mean=False):
+        assert isinstance(level, int) or level == "all" or level.endswith("-") \
+            or level.endswith("+")
+        self.level, self.p = level, p
+        self.key = [key] if isinstance(key, str) else key
+        self.inplace, self.to_mean = inplace, to_mean
+
+    def draw(self, nag):
+        params = {}
+        if self.p <= 0:
+            return params
+        on = _per_level(self.level, False, True, nag.num_levels)
+        for i in range(nag.num_levels):
+            if not on[i]:
+                continue
+            for k in self.key:
+                a = nag[i].get(k)
+                if a is None:
+                    break
+                if a.dim() != 2:
+                    raise IndexError(f"column dropout needs an [n, c] tensor, '{k}' is {tuple(a.shape)}")
+                c = a.shape[1]
+                if c > 64:
+                    raise ValueError("column dropout handles at most 64 columns")
+                drop = (torch.rand(c) < self.p).tolist()
+                params[(i, k)] = sum(1 << j for j, f in enumerate(drop) if f)
+        return params
+
+    def apply(self, nag, params):
+        return _dropout_apply(nag, columns=params, inplace=self.inplace, to_mean=self.to_mean)
+
+    def __call__(self, nag):
+        return self.apply(nag, self.draw(nag))
+
+
+class NAGDropoutRows:
+    """``NAGDropoutRows`` (src/transforms/data.py:546-648): every row of ``nag[i][key]`` is zeroed
+    (set to the column means with ``to_mean``) with probability ``p``; ``p <= 0`` does nothing;
+    ``inplace=False`` writes a new tensor.
+
+    One deliberate difference: with several keys and ``p > 0`` the reference builds one transform
+    per (level, key) and trips the length assertion of ``NAG.apply_data_transform``
+    (data.py:633-646, nag.py:816).  Here every present (level, key) pair gets its own draw.
+
+    ``draw``: one ``segment._draw_seed()`` per present (level, key); row ``r`` is dropped when
+    ``u(seed, r) < p``."""
+
+    def __init__(self, level="all", p=0.5, key=None, inplace=False, to_mean=False):
+        assert isinstance(level, int) or level == "all" or level.endswith("-") \
+            or level.endswith("+")
+        self.level, self.p = level, p
+        self.key = [key] if isinstance(key, str) else key
+        self.inplace, self.to_mean = inplace, to_mean
+
+    def draw(self, nag):
+        from .segment import _draw_seed
+        params = {}
+        if self.p <= 0:
+            return params
+        on = _per_level(self.level, False, True, nag.num_levels)
+        for i in range(nag.num_levels):
+            for k in self.key:
+                if on[i] and nag[i].get(k) is not None:
+                    params[(i, k)] = (float(self.p), _draw_seed())
+        return params
+
+    def apply(self, nag, params):
+        return _dropout_apply(nag, rows=params, inplace=self.inplace, to_mean=self.to_mean)
+
+    def __call__(self, nag):
+        return self.apply(nag, self.draw(nag))
+
+
+def _color_targets(data, keys, x_idx):
+    """[(name, tensor view)] a ColorTransform touches (src/transforms/point.py:387-400)."""
+    out = []
+    if x_idx is None:
+        for key in keys:
+            for k in (key, f"mean_{key}"):
+                t = data.get(k)
+                if t is not None:
+                    out.append((k, t))
+    elif data.x is not None:
+        out.append((("x", x_idx), data.x[:, x_idx:x_idx + 3]))
+    return out
+
+
+def _color_view(data, name):
+    return data.x[:, name[1]:name[1] + 3] if isinstance(name, tuple) else data[name]
+
+
+def _color_apply(nag, jitter=None, contrast=None, drop=None, new_tensor=False):
+    """``jitter`` {(level, name): (sigma, trunc, seed)}, ``contrast`` {(level, name): (blend,
+    1 - blend)}, ``drop`` {(level, name)}: one launch per tensor touched, plus the range launch of
+    a tensor that is contrasted."""
+    from . import augment as A
+    jitter, contrast, drop = jitter or {}, contrast or {}, drop or {}
+    for ln in list(dict.fromkeys(list(jitter) + list(contrast) + list(drop))):
+        i, name = ln
+        c = _f32(_color_view(nag[i], name), str(name))
+        out = torch.empty_like(c) if new_tensor and not isinstance(name, tuple) else None
+        A.color_(c, jitter=jitter.get(ln), contrast=contrast.get(ln), drop=ln in drop, out=out)
+        if out is not None:
+            nag[i][name] = out
+    return nag
+
+
+class NAGColorAutoContrast:
+    """``NAGColorAutoContrast`` (src/transforms/point.py:409-488): with probability ``p``,
+    ``rgb <- (1 - blend) * rgb + blend * (rgb - lo) / (hi - lo)`` with the per-column range of the
+    tensor.  Acts on ``rgb`` and ``mean_rgb`` (``KEYS = ['rgb']``), or on ``x[:, x_idx:x_idx + 3]``
+    in place.  Every tensor draws its OWN decision and, when ``blend is None``, its own blend
+    (``_func`` runs once per tensor).  A constant column gives the reference's NaN (0 / 0).
+
+    ``draw``: levels in order, tensors in the reference's order (key, then ``mean_`` key): one
+    ``torch.rand(1)`` per tensor (also at levels ``level`` excludes, where p = -1 never takes
+    it), then one more ``torch.rand(1)`` for the blend when it is taken and ``blend is None``."""
+    KEYS = ["rgb"]
+
+    def __init__(self, p=0.2, blend=None, x_idx=None, level="all"):
+        self.p, self.blend, self.x_idx, self.level = p, blend, x_idx, level
+
+    def draw(self, nag):
+        level_p = _per_level(self.level, -1, self.p, nag.num_levels)
+        params = {}
+        for i in range(nag.num_levels):
+            for name, _ in _color_targets(nag[i], self.KEYS, self.x_idx):
+                if not bool(torch.rand(1) < level_p[i]):
+                    continue
+                if self.blend is None:
+                    b = torch.rand(1)
+                    params[(i, name)] = (float(b), float(1 - b))
+                else:
+                    params[(i, name)] = (float(self.blend), 1.0 - float(self.blend))
+        return params
+
+    def apply(self, nag, params):
+        return _color_apply(nag, contrast=params, new_tensor=True)
+
+    def __call__(self, nag):
+        return self.apply(nag, self.draw(nag))
+
+
+class NAGColorDrop:
+    """``NAGColorDrop`` (src/transforms/point.py:491-545): with probability ``p`` a colour tensor
+    is multiplied by 0 in place (``rgb *= 0``: negative values give -0, NaN stays NaN).  Acts on
+    ``rgb``, ``lab``, ``hsv`` and their ``mean_`` twins, or on ``x[:, x_idx:x_idx + 3]``; every
+    tensor draws its own decision.
+
+    ``draw``: one ``torch.rand(1)`` per tensor, levels in order, keys ``rgb, mean_rgb, lab,
+    mean_lab, hsv, mean_hsv``."""
+    KEYS = ["rgb", "lab", "hsv"]
+
+    def __init__(self, p=0.2, x_idx=None, level="all"):
+        self.p, self.x_idx, self.level = p, x_idx, level
+
+    def draw(self, nag):
+        level_p = _per_level(self.level, -1, self.p, nag.num_levels)
+        params = {}
+        for i in range(nag.num_levels):
+            for name, _ in _color_targets(nag[i], self.KEYS, self.x_idx):
+                if bool(torch.rand(1) < level_p[i]):
+                    params[(i, name)] = True
+        return params
+
+    def apply(self, nag, params):
+        return _color_apply(nag, drop=params)
+
+    def __call__(self, nag):
+        return self.apply(nag, self.draw(nag))
+
+
+class GeometricAugmentation:
+    """``NAGJitterKey('pos', pos_jitter, trunc)`` + ``RandomTiltAndRotate(phi, theta)`` +
+    ``RandomAnisotropicScale(delta)`` + ``RandomAxisFlip(flip_axis, flip_p)`` (default.yaml:
+    250-264) as one launch per tensor.  ``draw`` is the four ``draw``s in that order, so under one
+    ``torch.manual_seed`` the result equals the stepwise chain bit for bit."""
+
+    def __init__(self, pos_jitter=0.01, trunc=0.05, phi=5, theta=180, delta=0.2, flip_axis=0,
+                 flip_p=0.5):
+        self.jitter = NAGJitterKey(key="pos", sigma=pos_jitter, trunc=trunc)
+        self.tilt = RandomTiltAndRotate(phi=phi, theta=theta)
+        self.scale = RandomAnisotropicScale(delta=delta)
+        self.flip = RandomAxisFlip(axis=flip_axis, p=flip_p)
+
+    def draw(self, nag):
+        return {"jitter": self.jitter.draw(nag), "tilt": self.tilt.draw(nag),
+                "scale": self.scale.draw(nag), "flip": self.flip.draw(nag)}
+
+    def apply(self, nag, params):
+        jitter = {i: v for (i, _), v in params["jitter"].items()}
+        return _geometry_apply(nag, jitter=jitter, tilt=params["tilt"], scale=params["scale"],
+                               flip=params["flip"])
+
+    def __call__(self, nag):
+        return self.apply(nag, self.draw(nag))
+
+
+class FeatureAugmentation:
+    """``NAGJitterKey(key, sigma, trunc)`` + ``NAGDropoutColumns(p=p_columns, key=key,
+    inplace=True)`` + ``NAGDropoutRows(p=p_rows, key=key, inplace=True)`` (default.yaml:293-340
+    for one group of keys) as one launch per tensor, in place.  ``draw`` is the three ``draw``s in
+    that order."""
+
+    def __init__(self, key=None, sigma=0.01, trunc=0.02, p_columns=0.0, p_rows=0.0, level="all"):
+        self.jitter = NAGJitterKey(key=key, sigma=sigma, trunc=trunc)
+        self.columns = NAGDropoutColumns(level=level, p=p_columns, key=key, inplace=True)
+        self.rows = NAGDropoutRows(level=level, p=p_rows, key=key, inplace=True)
+
+    def draw(self, nag):
+        return {"jitter": self.jitter.draw(nag), "columns": self.columns.draw(nag),
+                "rows": self.rows.draw(nag)}
+
+    def apply(self, nag, params):
+        return _dropout_apply(nag, columns=params["columns"], rows=params["rows"],
+                              jitter=params["jitter"], inplace=True)
+
+    def __call__(self, nag):
+        return self.apply(nag, self.draw(nag))
+
+
+class ColorAugmentation:
+    """``NAGJitterKey('rgb', sigma, trunc)`` + ``NAGColorAutoContrast(p_contrast, blend)`` +
+    ``NAGColorDrop(p_drop)`` (default.yaml:348-358) as one launch per tensor touched, plus the
+    range launch of a tensor that is contrasted (the range is that of the JITTERED colours, which
+    the range kernel recomputes instead of storing).  ``draw`` is the three ``draw``s in that
+    order."""
+
+    def __init__(self, sigma=0.01, trunc=0.02, p_contrast=0.2, blend=None, p_drop=0.2,
+                 level="all"):
+        self.jitter = NAGJitterKey(key="rgb", sigma=sigma, trunc=trunc)
+        self.contrast = NAGColorAutoContrast(p=p_contrast, blend=blend, level=level)
+        self.drop = NAGColorDrop(p=p_drop, level=level)
+
+    def draw(self, nag):
+        return {"jitter": self.jitter.draw(nag), "contrast": self.contrast.draw(nag),
+                "drop": self.drop.draw(nag)}
+
+    def apply(self, nag, params):
+        return _color_apply(nag, jitter=params["jitter"], contrast=params["contrast"],
+                            drop=params["drop"])
+
+    def __call__(self, nag):
+        return self.apply(nag, self.draw(nag))
