@@ -295,7 +295,8 @@ int spt_graphnorm_bwd_acc_f32(const float* x, const float* gy, const int64_t* ba
  *   out [n, H*Dv]; m, z [n, H]: running max / sum of the softmax, saved for
  *              the backward (both NULL to skip).
  * Built shapes: H*D <= 128, H*Dv <= 128, F in {18, 32}; anything else returns
- * an error (never a silent fallback).  Forward is deterministic.
+ * an error.  Which kernel a built shape runs on is decided by the mode word and
+ * the route table further down.  Forward is deterministic.
  * Backward: gout [n, H*Dv] -> gqkv [n, ld] (zero-filled here; k/v columns use
  * f32 atomics), gedge_attr [e, F], and the six RPE parameter gradients
  * (NULL to skip one).  ws: spt_edge_attn_bwd_workspace_bytes().
@@ -320,7 +321,7 @@ size_t spt_edge_attn_bwd_workspace_bytes(int H, int D, int Dv, int F);
  * only, nothing changes); tests cross-check all three at full scene size. */
 int spt_attn_use_mfma(int mode);
 /* Backward tiling of the bf16-pipe modes (2, 3): 2 (default) = the edge-lane kernel described
- * below when the caller's workspace allows it (else 1); 1 = 16-edge tiles over the edge
+ * below where the route table allows it; 1 = 16-edge tiles over the edge
  * stream, at most two consecutive source nodes per pass, tiles 100 % full (dq by atomicAdd: a
  * node may be cut between two waves); 0 = one tile set per source node (62-69 % full at mean
  * degree 16).  Same results up to f32 summation order.  Returns the previous setting. */
@@ -408,23 +409,57 @@ int spt_edge_attn_bwd_acc_f32(const float* qkv, int64_t n, int H, int D, int Dv,
                               float* gbk, float* gWq, float* gbq, float* gWv, float* gbv,
                               void* ws, size_t ws_bytes, spt_stream_t stream);
 
-/* Per-call formulation: the *_ex entries take a `mode` word instead of reading the process-wide
- * switches above, so two callers (two models at different precisions, two streams) never change
- * each other's arithmetic.  mode < 0 (SPT_ATTN_DEFAULT): the process defaults.  Otherwise
+/* The mode word.  The *_ex / *_m entries take a `mode` word that carries the formulation per call:
  *   bits 0-1  precision: SPT_ATTN_VALU 0, SPT_ATTN_F32 1 (f32 matrix pipe), SPT_ATTN_SPLIT_BF16 2,
  *             SPT_ATTN_BF16 3 (operands rounded to bf16);
- *   bits 4-5  backward tiling of the bf16-pipe precisions: 0 auto (edge-lane when the workspace
- *             allows), SPT_ATTN_BWD_PER_NODE, SPT_ATTN_BWD_PACKED, SPT_ATTN_BWD_EDGE_LANE;
- *   bits 6-7  edge order of the edge-lane backward: 0 = the process default
- *             (spt_attn_bwd_el_target_order), SPT_ATTN_BWD_TARGET_ORDER (csrc/edge_attn_to.hip:
- *             dk / dv reduced per target inside the tile, a few float atomics per node - the
- *             sums' order, not their value, varies run to run), SPT_ATTN_BWD_SOURCE_ORDER
- *             (csrc/edge_attn_el.hip: no atomics, every gradient bitwise reproducible).  The
- *             tile records a caller pre-builds must come from spt_attn_pack_tile_ids_m with the
- *             SAME word (64 ints per tile in target order, 48 in source order); when a call
- *             cannot run the selected target order (src_sorted NULL or a workspace below
- *             spt_edge_attn_bwd_ex_workspace_bytes) it falls back to the source order and
- *             rebuilds the records itself - it never reads records of the other format.
+ *   bits 4-5  backward form of the bf16-pipe precisions: 0 open, SPT_ATTN_BWD_PER_NODE,
+ *             SPT_ATTN_BWD_PACKED, SPT_ATTN_BWD_EDGE_LANE;
+ *   bits 6-7  edge order of the edge-lane backward: 0 open, SPT_ATTN_BWD_TARGET_ORDER
+ *             (csrc/edge_attn_to.hip: dk / dv reduced per target inside the tile, a few float
+ *             atomics per node - the sums' order, not their value, varies run to run),
+ *             SPT_ATTN_BWD_SOURCE_ORDER (csrc/edge_attn_el.hip: no atomics, every gradient
+ *             bitwise reproducible).
+ * mode < 0 (SPT_ATTN_DEFAULT) leaves all three fields open.  An OPEN field is filled from the
+ * process defaults (spt_attn_use_mfma, spt_attn_bwd_packed, spt_attn_bwd_el_target_order) at the
+ * moment of the call.  spt_attn_resolve_mode(mode) does that and returns the fully explicit word:
+ * it is the one function of the library that reads those three switches, every entry that takes
+ * a mode word resolves it once on entry and works on the result, and a caller that resolves the
+ * word itself and hands the result to every later call (forward, tile records, backward) is
+ * independent of the switches from then on - two callers (two models at different precisions,
+ * two streams) never change each other's arithmetic.  The resolver marks the fields IT filled in
+ * (SPT_ATTN_FORM_OPEN, SPT_ATTN_ORDER_OPEN): such a field is a preference, one the caller wrote is
+ * a demand (below).  Resolving is idempotent; bits outside the fields and marks are dropped.
+ *
+ * Route of the backward (spt_edge_attn_bwd_ex_f32), from the resolved word (precision p, form,
+ * order), the shape and the operands the caller hands over.  "Built shape" = H 16, D 4, Dv 4, F 32
+ * with edge_attr and all three encoders; tables = spt_edge_attn_bwd_workspace_bytes; ex =
+ * tables + the scratch of the edge order in question (spt_edge_attn_bwd_ex_workspace_bytes covers
+ * both orders).
+ *   VALU     p == 0, or not the built shape: the generic lane-per-output kernels (a shape outside
+ *            their compiled cases returns -4; without edge_attr F counts as 32);
+ *   TARGET   form edge lane, p >= 2, e > 0, order target, src_sorted given, the target view
+ *            (tperm, trowptr) or target-order tile_ids given, ws_bytes >= ex: csrc/edge_attn_to.hip;
+ *   SOURCE   form edge lane, p >= 2, e > 0, not TARGET, the target view given, ws_bytes >= ex:
+ *            csrc/edge_attn_el.hip;
+ *   PACKED   none of the above, p >= 2, form not per node, e > 0: packed tiles over the edge stream;
+ *   PER_NODE everything else on the built shape (p == 1 - the only f32-pipe backward -, form per
+ *            node, e == 0): one tile set per source node.
+ * The downgrades of an open field are silent, and these are all of them:
+ *   order target -> SOURCE   src_sorted missing or ws_bytes below the target order's need, with
+ *                            the view given (tile_ids, being target-order records, are ignored and
+ *                            rebuilt in the workspace - no kernel reads records of the other format);
+ *   edge lane -> PACKED      no view and no usable records, or ws_bytes below the order's need;
+ *   edge lane -> PER_NODE    p == 1, or e == 0;
+ *   packed -> PER_NODE       p == 1, or e == 0.
+ * A field the CALLER wrote refuses instead (-1), on the built shape with p != 0: SPT_ATTN_BWD_EDGE_LANE
+ * when the route is neither TARGET nor SOURCE; SPT_ATTN_BWD_TARGET_ORDER when an edge-lane route is
+ * possible (form edge lane, p >= 2, e > 0, view or records + src_sorted) but TARGET is not.  tperm
+ * and trowptr come both or neither.  VALU, PER_NODE and PACKED zero gqkv first (they add into it).
+ * spt_edge_attn_bwd_route answers the same question without launching anything - the entry
+ * itself switches on the same function's result: `operands` = SPT_ATTN_HAS_* of what the call will
+ * be given (SPT_ATTN_HAS_RPE: edge_attr and all three encoders; F <= 0: no edge_attr), the result
+ * one of SPT_ATTN_ROUTE_* or the negative status the launch would return (spt_last_error() set).
+ *
  * Edge-lane backward (csrc/edge_attn_el.hip; H=16, D=Dv=4, F=32): 16-edge tiles over the CSR edge
  * stream, a wave owns half of the heads; the recompute GEMM runs transposed so that a lane holds
  * whole heads of ONE edge (no redundant softmax math, per-edge node rows fetched by LDS-DMA, any
@@ -437,8 +472,7 @@ int spt_edge_attn_bwd_acc_f32(const float* qkv, int64_t n, int H, int D, int Dv,
  * by the same pass (two 256 B slots per tile), so no sum depends on the order the waves run in.
  * It needs the scratch of spt_edge_attn_bwd_ex_workspace_bytes(n, e, ...)
  * (per-node rows + 512 B per edge + 512 B per tile), that view, and optionally src_sorted [e] int32 =
- * edge_index[0] in CSR order (NULL: rebuilt from erowptr).  Without the view or the workspace the
- * packed kernel runs instead.
+ * edge_index[0] in CSR order (NULL: rebuilt from erowptr).
  * With gedge_attr_accumulate == 0 the edge-lane kernel zero-fills gedge_attr first (both waves of
  * a pair add their halves). */
 #define SPT_ATTN_DEFAULT (-1)
@@ -451,6 +485,20 @@ int spt_edge_attn_bwd_acc_f32(const float* qkv, int64_t n, int H, int D, int Dv,
 #define SPT_ATTN_BWD_EDGE_LANE (3 << 4)
 #define SPT_ATTN_BWD_TARGET_ORDER (1 << 6)
 #define SPT_ATTN_BWD_SOURCE_ORDER (2 << 6)
+#define SPT_ATTN_FORM_OPEN (1 << 8)  /* set by the resolver: bits 4-5 hold the process default */
+#define SPT_ATTN_ORDER_OPEN (1 << 9) /* set by the resolver: bits 6-7 hold the process default */
+int spt_attn_resolve_mode(int mode);
+#define SPT_ATTN_HAS_RPE 1
+#define SPT_ATTN_HAS_SRC 2
+#define SPT_ATTN_HAS_TILE_IDS 4
+#define SPT_ATTN_HAS_TARGET_VIEW 8
+#define SPT_ATTN_ROUTE_VALU 0
+#define SPT_ATTN_ROUTE_PER_NODE 1
+#define SPT_ATTN_ROUTE_PACKED 2
+#define SPT_ATTN_ROUTE_EDGE_LANE_SOURCE 3
+#define SPT_ATTN_ROUTE_EDGE_LANE_TARGET 4
+int spt_edge_attn_bwd_route(int64_t n, int64_t e, int H, int D, int Dv, int F, int operands, int mode,
+                            size_t ws_bytes);
 int spt_edge_attn_fwd_ex_f32(const float* qkv, int64_t n, int H, int D, int Dv,
                              const int32_t* erowptr, const int32_t* eperm,
                              const int32_t* tgt_sorted, int64_t e,
@@ -463,8 +511,8 @@ int spt_edge_attn_fwd_ex_f32(const float* qkv, int64_t n, int H, int D, int Dv,
  * target order needs 644 B per node + 256 B per edge + 16 B per tile id, the source order
  * 388 B per node + 516 B per edge + 12 B per tile id) on top of the weight-gradient tables. */
 size_t spt_edge_attn_bwd_ex_workspace_bytes(int64_t n, int64_t e, int H, int D, int Dv, int F);
-/* 1 when the edge-lane backward is built for this head layout AND `mode` (< 0: the process
- * defaults) selects it (a caller uses it to decide whether to build the target view). */
+/* 1 when the edge-lane backward is built for this head layout AND the resolved `mode` selects it
+ * (form edge lane, a bf16-pipe precision). */
 int spt_edge_attn_bwd_el_supported(int H, int D, int Dv, int F, int mode);
 /* [ceil(e / 16)][48] int32 tile records of the edge-lane backward (edge rows | targets | sources of
  * 16 consecutive CSR positions): depends on the graph only, built once per batch and level by the

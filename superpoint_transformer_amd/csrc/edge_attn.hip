@@ -18,6 +18,7 @@
 #include <stdlib.h>
 
 #include "common.hpp"
+#include "edge_attn_internal.hpp"
 
 namespace spt {
 
@@ -750,117 +751,82 @@ static bool attn_shape(int H, int D, int Dv, int qpl, int vpl, AttnShape* sh) {
 
 static inline int per_lane(int total) { return total <= 64 ? 1 : (total <= 128 ? 2 : 0); }
 
-}  // namespace spt
+// The compiled cases of the generic VALU kernels: fn(sh, AttnCase<Q, V, FF>) runs for the one that
+// fits (H, D, Dv, F); false when none does.
+template <int Q, int V, int FF> struct AttnCase { static constexpr int q = Q, v = V, f = FF; };
+template <class Fn>
+static bool attn_valu_case(int H, int D, int Dv, int F, Fn&& fn) {
+  const int qpl = per_lane(H * D), vpl = per_lane(H * Dv);
+  AttnShape sh;
+#define SPT_ATTN_CASE(Q, V, FF)                                                        \
+  if (qpl == Q && vpl == V && F == FF && attn_shape(H, D, Dv, Q, V, &sh))              \
+    return fn(sh, AttnCase<Q, V, FF>{}), true;
+  SPT_ATTN_CASE(1, 1, 32)
+  SPT_ATTN_CASE(1, 2, 32)
+  SPT_ATTN_CASE(2, 2, 32)
+  SPT_ATTN_CASE(1, 1, 16)  /* nano: 16-D edge encodings */
+  SPT_ATTN_CASE(1, 1, 18)
+  SPT_ATTN_CASE(1, 2, 18)
+  SPT_ATTN_CASE(2, 2, 18)
+#undef SPT_ATTN_CASE
+  return false;
+}
+static const char* const ATTN_UNBUILT =
+    "unsupported attention shape (built: H*D<=128, H*Dv<=128, F in {18,32}; F=16 with H*D, H*Dv <= 64)";
+static int attn_refuse(const char* who, int code, const char* why, int H, int D, int Dv, int F) {
+  return fail(code, "%s: %s [H=%d D=%d Dv=%d F=%d]", who, why, H, D, Dv, F);
+}
 
-namespace spt {
-// edge_attn_mfma.hip: matrix-pipe formulation for the SPT-64 head layout
-bool attn_mfma_shape_ok(int H, int D, int Dv, int F, const void* ea, const void* Wk,
-                        const void* Wq, const void* Wv);
-void attn_fwd_mfma_launch(const float* qkv, int64_t n, const int32_t* erowptr,
-                          const int32_t* eperm, const int32_t* tgt, const float* ea,
-                          const float* Wk, const float* bk, const float* Wq, const float* bq,
-                          const float* Wv, const float* bv, int scale_mode, float scale_a,
-                          float* out, float* m, float* z, int split_bf16, hipStream_t stream);
-int attn_bwd_mfma_launch(const float* qkv, int64_t n, const int32_t* erowptr,
-                         const int32_t* eperm, const int32_t* tgt, const float* ea,
-                         const float* Wk, const float* bk, const float* Wq, const float* bq,
-                         const float* Wv, const float* bv, int scale_mode, float scale_a,
-                         const float* out, const float* m, const float* z, const float* gout,
-                         float* gqkv, float* gea, int gea_acc, float* partial, int split_bf16,
-                         int64_t e, int packed, hipStream_t stream);
-// edge_attn_el.hip: edge-lane backward (two waves per SIMD)
-size_t attn_bwd_el_workspace_bytes(int64_t n, int64_t e);
-void attn_pack_tile_ids_launch(const int32_t* eperm, const int32_t* tgt, const int32_t* src,
-                               int64_t e, int32_t* ids3, hipStream_t stream);
-// edge_attn_to.hip: the same backward over the edge stream in TARGET order
-bool attn_bwd_to_enabled();
-size_t attn_bwd_to_workspace_bytes(int64_t n, int64_t e);
-void attn_pack_tile_ids_to_launch(const int32_t* eperm, const int32_t* tgt, const int32_t* src,
-                                  const int32_t* tperm, int64_t e, int32_t* ids4, hipStream_t stream);
-// XCD bands of the attention kernels' work distribution (edge_attn_mfma.hip forward, edge_attn_to.hip
-// backward): a SPEED choice between two walks of the same work - read once from the environment
-// (SPT_ATTN_XCD_BANDS=0 restores the plain grid stride / contiguous tile ranges for A/B runs).
-bool attn_xcd_bands() {
-  static const bool on = [] { const char* e = getenv("SPT_ATTN_XCD_BANDS"); return e ? atoi(e) != 0 : true; }();
-  return on;
-}
-int attn_mirror_prepare_launch(const int64_t* ei, const int32_t* eperm, int64_t e, int64_t pairs,
-                               int32_t* inv, int32_t* flag, hipStream_t stream);
-void attn_pack_tile_ids_mirror_launch(const int32_t* eperm, const int32_t* tgt, const int32_t* src,
-                                      const int32_t* inv, int64_t e, int64_t pairs, int32_t* ids4,
-                                      hipStream_t stream);
-int attn_bwd_to_launch(const float* qkv, int64_t n, const int32_t* erowptr, const int32_t* eperm,
-                       const int32_t* tgt, const int32_t* src, const int32_t* tile_ids,
-                       const int32_t* tperm, int64_t e, const float* ea, const float* Wk,
-                       const float* bk, const float* Wq, const float* bq, const float* Wv,
-                       const float* bv, int scale_mode, float scale_a, const float* out,
-                       const float* m, const float* z, const float* gout, float* gqkv, float* gea,
-                       int gea_acc, float* partial, void* ws, int prec, hipStream_t stream);
-int attn_bwd_el_launch(const float* qkv, int64_t n, const int32_t* erowptr, const int32_t* eperm,
-                       const int32_t* tgt, const int32_t* src, const int32_t* tile_ids,
-                       const int32_t* tperm, const int32_t* trowptr, int64_t e, const float* ea,
-                       const float* Wk, const float* bk, const float* Wq, const float* bq,
-                       const float* Wv, const float* bv, int scale_mode, float scale_a,
-                       const float* out, const float* m, const float* z, const float* gout,
-                       float* gqkv, float* gea, int gea_acc, float* partial, void* ws, int prec,
-                       hipStream_t stream);
-// 0: lane-per-output VALU kernels, 1: f32 matrix pipe (bitwise an fmaf chain), 2 (default):
-// split-bf16 on the bf16 matrix pipe (3 products per f32 product, ~2^-17 relative per product: 17 of f32's 24 bits), 3: plain
-// bf16 operands, f32 accumulate (the bf16 precision mode)
-static std::atomic<int> g_attn_mfma{-1};  // -1: decide from the environment on first use
-static int mfma_mode() {
-  if (g_attn_mfma < 0) g_attn_mfma = getenv("SPT_ATTN_VALU_ONLY") == nullptr ? 2 : 0;
-  return g_attn_mfma;
-}
-static bool use_mfma() { return mfma_mode() != 0; }
-// backward of the bf16-pipe modes: 2 (default) edge-lane kernel (edge_attn_el.hip; needs the
-// larger workspace of spt_edge_attn_bwd_ex_workspace_bytes, else 1 is used), 1 packed tiles over
-// the edge stream, 0 one tile set per source node
+// ---- the mode word ---------------------------------------------------------------------------
+// Process defaults of the three fields of the mode word (include/spt_hip.h).  spt_attn_resolve_mode
+// is the ONLY reader: everything else works on the word it returns.
+//   precision: 0 VALU kernels, 1 f32 matrix pipe (bitwise an fmaf chain), 2 (default) split-bf16 on the
+//   bf16 matrix pipe, 3 plain bf16 operands, f32 accumulate; -1: SPT_ATTN_VALU_ONLY decides on first use
+static std::atomic<int> g_attn_mfma{-1};
+//   backward form of the bf16-pipe precisions: 2 (default) edge lane, 1 packed, 0 per node
 static std::atomic<int> g_attn_bwd_packed{2};
-// per-call mode word (include/spt_hip.h): < 0 = the process defaults above
-static int mode_precision(int mode) { return mode < 0 ? mfma_mode() : (mode & 3); }
-static int mode_bwd_form(int mode) {
-  const int f = mode < 0 ? 0 : ((mode >> 4) & 3);
-  return f == 0 ? (int)g_attn_bwd_packed : f - 1;
-}
-// bits 6-7 of the mode word: edge order of the edge-lane backward (0 = the process default of
-// spt_attn_bwd_el_target_order, SPT_ATTN_BWD_TARGET_ORDER, SPT_ATTN_BWD_SOURCE_ORDER)
-static bool mode_target_order(int mode) {
-  const int o = mode < 0 ? 0 : ((mode >> 6) & 3);
-  return o == 0 ? attn_bwd_to_enabled() : o == 1;
-}
+//   edge order of the edge-lane backward: 1 (default) by TARGET (edge_attn_to.hip), 0 by source
+//   (edge_attn_el.hip)
+static std::atomic<int> g_attn_el_target_order{[] { const char* e = getenv("SPT_EL_TARGET_ORDER"); return e ? (atoi(e) != 0) : 1; }()};
+
 }  // namespace spt
 
 using namespace spt;
 
-#define SPT_ATTN_DISPATCH(FN, ...)                                             \
-  do {                                                                         \
-    bool done__ = false;                                                       \
-    SPT_ATTN_CASE(FN, 1, 1, 32, __VA_ARGS__)                                   \
-    SPT_ATTN_CASE(FN, 1, 2, 32, __VA_ARGS__)                                   \
-    SPT_ATTN_CASE(FN, 2, 2, 32, __VA_ARGS__)                                   \
-    SPT_ATTN_CASE(FN, 1, 1, 16, __VA_ARGS__)  /* nano: 16-D edge encodings */  \
-    SPT_ATTN_CASE(FN, 1, 1, 18, __VA_ARGS__)                                   \
-    SPT_ATTN_CASE(FN, 1, 2, 18, __VA_ARGS__)                                   \
-    SPT_ATTN_CASE(FN, 2, 2, 18, __VA_ARGS__)                                   \
-    if (!done__)                                                               \
-      return ::spt::fail(-4, "%s: unsupported attention shape H=%d D=%d Dv=%d F=%d " \
-                         "(built: H*D<=128, H*Dv<=128, F in {18,32}; F=16 with H*D, H*Dv <= 64)", __func__, H, D, Dv, F); \
-  } while (0)
-
-extern "C" int spt_attn_bwd_packed(int on) {
-  const int prev = g_attn_bwd_packed;
-  g_attn_bwd_packed = on < 0 ? 0 : (on > 2 ? 2 : on);
-  return prev;
+extern "C" int spt_attn_resolve_mode(int mode) {
+  int word = mode < 0 ? 0 : mode & (3 | 3 << 4 | 3 << 6 | SPT_ATTN_FORM_OPEN | SPT_ATTN_ORDER_OPEN);
+  if (mode < 0) {
+    int p = g_attn_mfma;
+    if (p < 0) g_attn_mfma = p = getenv("SPT_ATTN_VALU_ONLY") == nullptr ? 2 : 0;
+    word = p;
+  }
+  if ((word & (3 << 4)) == 0) word |= ((g_attn_bwd_packed + 1) << 4) | SPT_ATTN_FORM_OPEN;
+  if ((word & (3 << 6)) == 0)
+    word |= (g_attn_el_target_order ? SPT_ATTN_BWD_TARGET_ORDER : SPT_ATTN_BWD_SOURCE_ORDER) | SPT_ATTN_ORDER_OPEN;
+  return word;
 }
 
+// The setters only write; what they return is read off the resolved default word.
 extern "C" int spt_attn_use_mfma(int mode) {
-  const int prev = mfma_mode();
+  const int prev = attn_mode_precision(spt_attn_resolve_mode(-1));
   if (mode < -1) return prev;            // query only
   g_attn_mfma = mode < 0 ? 0 : (mode > 3 ? 3 : mode);
   return prev;
 }
 
+extern "C" int spt_attn_bwd_packed(int on) {
+  const int prev = (attn_mode_form(spt_attn_resolve_mode(-1)) >> 4) - 1;
+  g_attn_bwd_packed = on < 0 ? 0 : (on > 2 ? 2 : on);
+  return prev;
+}
+
+extern "C" int spt_attn_bwd_el_target_order(int on) {
+  const int prev = attn_mode_target_order(spt_attn_resolve_mode(-1));
+  if (on >= 0) g_attn_el_target_order = on != 0;
+  return prev;
+}
+
+// ---- forward ---------------------------------------------------------------------------------
 extern "C" int spt_edge_attn_fwd_f32(const float* qkv, int64_t n, int H, int D, int Dv,
                                      const int32_t* erowptr, const int32_t* eperm,
                                      const int32_t* tgt_sorted, int64_t e,
@@ -882,38 +848,32 @@ extern "C" int spt_edge_attn_fwd_ex_f32(const float* qkv, int64_t n, int H, int 
                                         float scale_a, float* out, float* m, float* z, int mode,
                                         spt_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  const int prec = mode_precision(mode);
+  const int prec = attn_mode_precision(spt_attn_resolve_mode(mode));
   SPT_CHECK_ARG(n >= 0 && e >= 0 && H >= 1 && D >= 1 && Dv >= 1, "bad shape");
   if (n == 0) return 0;
   SPT_CHECK_ARG(qkv && erowptr && out && (tgt_sorted || e == 0), "null pointer");
   SPT_CHECK_ARG((m == nullptr) == (z == nullptr), "pass both m and z or neither");
-  if (prec != 0 && attn_mfma_shape_ok(H, D, Dv, F, edge_attr, Wk, Wq, Wv)) {
+  if (prec != 0 && attn_mfma_shape_ok(H, D, Dv, F, edge_attr && Wk && Wq && Wv)) {
     attn_fwd_mfma_launch(qkv, n, erowptr, eperm, tgt_sorted, edge_attr, Wk, bk, Wq, bq, Wv, bv,
-                         scale_mode, scale_a, out, m, z,
-                         prec == 2 ? 3 : (prec == 3 ? 1 : 0), stream);
+                         scale_mode, scale_a, out, m, z, attn_kernel_prec(prec), stream);
     SPT_CHECK_LAUNCH();
     return 0;
   }
   if (!edge_attr) F = 32;  // no RPE: any compiled F will do
-  const int qpl = per_lane(H * D), vpl = per_lane(H * Dv);
   const int ld = 2 * H * D + H * Dv;
   const int grid = (int)(ceil_div(n, EA_WAVES) < 256 * 8 ? ceil_div(n, EA_WAVES) : 256 * 8);
-#define SPT_ATTN_CASE(FN, Q, V, FF, ...)                                        \
-  if (!done__ && qpl == Q && vpl == V && F == FF) {                            \
-    AttnShape sh;                                                              \
-    if (attn_shape(H, D, Dv, Q, V, &sh)) {                                     \
-      FN<Q, V, FF><<<grid, EA_WAVES * 64, 0, stream>>>(__VA_ARGS__);           \
-      done__ = true;                                                           \
-    }                                                                          \
-  }
-  // `sh` is rebuilt inside each case; the kernel argument list refers to it
-  SPT_ATTN_DISPATCH(edge_attn_fwd_kernel, qkv, ld, n, sh, erowptr, eperm, tgt_sorted,
-                    edge_attr, Wk, bk, Wq, bq, Wv, bv, scale_mode, scale_a, out, m, z);
-#undef SPT_ATTN_CASE
+  if (!attn_valu_case(H, D, Dv, F, [&](const AttnShape& sh, auto c) {
+        using C = decltype(c);
+        edge_attn_fwd_kernel<C::q, C::v, C::f><<<grid, EA_WAVES * 64, 0, stream>>>(
+            qkv, ld, n, sh, erowptr, eperm, tgt_sorted, edge_attr, Wk, bk, Wq, bq, Wv, bv,
+            scale_mode, scale_a, out, m, z);
+      }))
+    return attn_refuse(__func__, -4, ATTN_UNBUILT, H, D, Dv, F);
   SPT_CHECK_LAUNCH();
   return 0;
 }
 
+// ---- backward: workspace, tile records --------------------------------------------------------
 constexpr int EA_BWD_BLOCKS = 256;  // one 4-wave workgroup per CU (1 wave per SIMD)
 
 static size_t attn_tables_bytes(int H, int D, int Dv, int F) {
@@ -925,11 +885,6 @@ extern "C" size_t spt_edge_attn_bwd_workspace_bytes(int H, int D, int Dv, int F)
   return attn_tables_bytes(H, D, Dv, F);
 }
 
-extern "C" int spt_edge_attn_bwd_el_supported(int H, int D, int Dv, int F, int mode) {
-  return H == 16 && D == 4 && Dv == 4 && F == 32 && mode_bwd_form(mode) == 2 &&
-         mode_precision(mode) >= 2;
-}
-
 extern "C" size_t spt_edge_attn_bwd_ex_workspace_bytes(int64_t n, int64_t e, int H, int D, int Dv,
                                                        int F) {
   // enough for EITHER edge order of the edge-lane backward: the target-order layout (640 B of
@@ -938,6 +893,140 @@ extern "C" size_t spt_edge_attn_bwd_ex_workspace_bytes(int64_t n, int64_t e, int
   return attn_tables_bytes(H, D, Dv, F) + (el > to ? el : to);
 }
 
+extern "C" int spt_edge_attn_bwd_el_supported(int H, int D, int Dv, int F, int mode) {
+  const int word = spt_attn_resolve_mode(mode);
+  return attn_mfma_shape_ok(H, D, Dv, F, true) && attn_mode_form(word) == SPT_ATTN_BWD_EDGE_LANE &&
+         attn_mode_precision(word) >= 2;
+}
+
+// [ceil(e / 16)][48] int32 tile records of the edge-lane backward: per 16 CSR positions the edge
+// rows (eperm, or the positions when NULL), targets and sources (positions beyond e repeat the last
+// edge).  Depends on the graph only: a caller builds it once per batch and level and hands it to
+// spt_edge_attn_bwd_ex_f32 (which otherwise rebuilds it in its workspace on every call).
+extern "C" int spt_attn_pack_tile_ids(const int32_t* eperm, const int32_t* tgt_sorted,
+                                      const int32_t* src_sorted, int64_t e, int32_t* tile_ids,
+                                      spt_stream_t stream_) {
+  SPT_CHECK_ARG(e >= 0 && (e == 0 || (tgt_sorted && src_sorted && tile_ids)), "null pointer");
+  // the 48-int source-order records: the target-order backward (the default) reads another format
+  // and would silently walk garbage - refuse instead of writing records nobody can use
+  SPT_CHECK_ARG(!attn_mode_target_order(spt_attn_resolve_mode(-1)),
+                "the target-order backward is on: build the tile records with spt_attn_pack_tile_ids_ex / "
+                "_m (or switch it off with spt_attn_bwd_el_target_order(0))");
+  attn_pack_tile_ids_launch(eperm, tgt_sorted, src_sorted, e, tile_ids, (hipStream_t)stream_);
+  SPT_CHECK_LAUNCH();
+  return 0;
+}
+
+// Tile records in the format the edge order of `mode` reads: 64 ints per tile in TARGET order (needs
+// `tperm`, the CSR view of the targets over the CSR positions, and `src_sorted`), else the 48-int
+// source-order records.  The plain and _ex entries are the same under the process defaults.
+extern "C" int spt_attn_tile_record_ints_m(int mode) {
+  return attn_mode_target_order(spt_attn_resolve_mode(mode)) ? 64 : 48;
+}
+extern "C" int spt_attn_tile_record_ints(void) { return spt_attn_tile_record_ints_m(-1); }
+extern "C" int spt_attn_pack_tile_ids_m(const int32_t* eperm, const int32_t* tgt_sorted,
+                                        const int32_t* src_sorted, const int32_t* tperm, int64_t e,
+                                        int mode, int32_t* tile_ids, spt_stream_t stream_) {
+  SPT_CHECK_ARG(e >= 0 && (e == 0 || (tgt_sorted && src_sorted && tile_ids)), "null pointer");
+  if (attn_mode_target_order(spt_attn_resolve_mode(mode))) {
+    SPT_CHECK_ARG(e == 0 || tperm, "target-order tile records need the target view (tperm)");
+    attn_pack_tile_ids_to_launch(eperm, tgt_sorted, src_sorted, tperm, e, tile_ids, (hipStream_t)stream_);
+  } else {
+    attn_pack_tile_ids_launch(eperm, tgt_sorted, src_sorted, e, tile_ids, (hipStream_t)stream_);
+  }
+  SPT_CHECK_LAUNCH();
+  return 0;
+}
+extern "C" int spt_attn_pack_tile_ids_ex(const int32_t* eperm, const int32_t* tgt_sorted,
+                                         const int32_t* src_sorted, const int32_t* tperm, int64_t e,
+                                         int32_t* tile_ids, spt_stream_t stream_) {
+  return spt_attn_pack_tile_ids_m(eperm, tgt_sorted, src_sorted, tperm, e, -1, tile_ids, stream_);
+}
+
+// Target-order tile records from the MIRROR structure of the edge list instead of a sorted target
+// view (edge_attn_to.hip): `edge_index` = the [2, e] int64 list as the reference hands it over,
+// `pairs` = M with edge i < M mirrored at i + M and every edge from 2 M on a self loop.
+// spt_attn_mirror_prepare writes inv [e] (the inverse of eperm) and ORs into *flag (int32, device;
+// the caller clears it): bit 0 = a pair that is not (s, t) / (t, s), bit 1 = a loop with s != t.
+// spt_attn_pack_tile_ids_mirror then writes the same 64-int records spt_attn_pack_tile_ids_m
+// writes in target order (the edges into a node in another order: sums of the same terms).
+extern "C" int spt_attn_mirror_prepare(const int64_t* edge_index, const int32_t* eperm, int64_t e,
+                                       int64_t pairs, int32_t* inv, int32_t* flag,
+                                       spt_stream_t stream_) {
+  SPT_CHECK_ARG(e >= 0 && pairs >= 0 && 2 * pairs <= e, "bad shape");
+  SPT_CHECK_ARG(e == 0 || (edge_index && eperm && inv && flag), "null pointer");
+  attn_mirror_prepare_launch(edge_index, eperm, e, pairs, inv, flag, (hipStream_t)stream_);
+  SPT_CHECK_LAUNCH();
+  return 0;
+}
+extern "C" int spt_attn_pack_tile_ids_mirror(const int32_t* eperm, const int32_t* tgt_sorted,
+                                             const int32_t* src_sorted, const int32_t* inv,
+                                             int64_t e, int64_t pairs, int32_t* tile_ids,
+                                             spt_stream_t stream_) {
+  SPT_CHECK_ARG(e >= 0 && pairs >= 0 && 2 * pairs <= e, "bad shape");
+  SPT_CHECK_ARG(e == 0 || (eperm && tgt_sorted && src_sorted && inv && tile_ids), "null pointer");
+  attn_pack_tile_ids_mirror_launch(eperm, tgt_sorted, src_sorted, inv, e, pairs, tile_ids,
+                                   (hipStream_t)stream_);
+  SPT_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- backward: the route -----------------------------------------------------------------------
+// Which backward a call runs, from the RESOLVED word, the shape and what the caller hands over
+// (SPT_ATTN_HAS_*): the table of include/spt_hip.h.  Pure: a negative result is the refusal's status,
+// *why its text.  A field the resolver filled (SPT_ATTN_*_OPEN) downgrades, one the caller wrote refuses.
+static int attn_bwd_route(int64_t n, int64_t e, int H, int D, int Dv, int F, int operands, int word,
+                          size_t ws_bytes, const char** why) {
+  const int prec = attn_mode_precision(word), form = attn_mode_form(word);
+  const bool rpe = operands & SPT_ATTN_HAS_RPE, src = operands & SPT_ATTN_HAS_SRC,
+             ids = operands & SPT_ATTN_HAS_TILE_IDS, view = operands & SPT_ATTN_HAS_TARGET_VIEW;
+  if (prec == 0 || !attn_mfma_shape_ok(H, D, Dv, F, rpe)) {
+    if (attn_valu_case(H, D, Dv, F, [](const AttnShape&, auto) {})) return SPT_ATTN_ROUTE_VALU;
+    *why = ATTN_UNBUILT;
+    return -4;
+  }
+  // (target order: the sorted target view or ready-made tile records; source order: the view)
+  const bool target = attn_mode_target_order(word);
+  const bool el_possible = form == SPT_ATTN_BWD_EDGE_LANE && prec >= 2 && e > 0 &&
+                           (view || (target && ids && src));
+  // each edge order has its own scratch layout: a route only runs inside the bytes it needs
+  const size_t tables = attn_tables_bytes(H, D, Dv, F);
+  int route;
+  if (el_possible && target && src && ws_bytes >= tables + attn_bwd_to_workspace_bytes(n, e))
+    route = SPT_ATTN_ROUTE_EDGE_LANE_TARGET;
+  else if (el_possible && view && ws_bytes >= tables + attn_bwd_el_workspace_bytes(n, e))
+    route = SPT_ATTN_ROUTE_EDGE_LANE_SOURCE;
+  else if (prec >= 2 && form != SPT_ATTN_BWD_PER_NODE && e > 0)
+    route = SPT_ATTN_ROUTE_PACKED;
+  else
+    route = SPT_ATTN_ROUTE_PER_NODE;
+  // (an edge-lane route implies its view or records: el_possible)
+  if (form == SPT_ATTN_BWD_EDGE_LANE && !(word & SPT_ATTN_FORM_OPEN) &&
+      route != SPT_ATTN_ROUTE_EDGE_LANE_TARGET && route != SPT_ATTN_ROUTE_EDGE_LANE_SOURCE) {
+    *why = "edge-lane backward: workspace of spt_edge_attn_bwd_ex_workspace_bytes, the "
+           "target CSR view (or target-order tile records) and a bf16-pipe precision are required";
+    return -1;
+  }
+  if (target && !(word & SPT_ATTN_ORDER_OPEN) && el_possible && route != SPT_ATTN_ROUTE_EDGE_LANE_TARGET) {
+    *why = "target-order backward: src_sorted and the workspace of "
+           "spt_edge_attn_bwd_ex_workspace_bytes are required";
+    return -1;
+  }
+  return route;
+}
+
+extern "C" int spt_edge_attn_bwd_route(int64_t n, int64_t e, int H, int D, int Dv, int F, int operands,
+                                       int mode, size_t ws_bytes) {
+  SPT_CHECK_ARG(n >= 0 && e >= 0 && H >= 1 && D >= 1 && Dv >= 1, "bad shape");
+  if (F <= 0) F = 32;  // no edge_attr
+  SPT_CHECK_ARG(!(operands & SPT_ATTN_HAS_RPE) || ws_bytes >= attn_tables_bytes(H, D, Dv, F),
+                "workspace too small");
+  const char* why = nullptr;
+  const int route = attn_bwd_route(n, e, H, D, Dv, F, operands, spt_attn_resolve_mode(mode), ws_bytes, &why);
+  return route < 0 ? attn_refuse(__func__, route, why, H, D, Dv, F) : route;
+}
+
+// ---- backward: the entries -----------------------------------------------------------------------
 extern "C" int spt_edge_attn_bwd_f32(const float* qkv, int64_t n, int H, int D, int Dv,
                                      const int32_t* erowptr, const int32_t* eperm,
                                      const int32_t* tgt_sorted, int64_t e,
@@ -978,186 +1067,78 @@ extern "C" int spt_edge_attn_bwd_acc_f32(const float* qkv, int64_t n, int H, int
                                   ws_bytes, stream_);
 }
 
-// [ceil(e / 16)][48] int32 tile records of the edge-lane backward: per 16 CSR positions the edge
-// rows (eperm, or the positions when NULL), targets and sources (positions beyond e repeat the last
-// edge).  Depends on the graph only: a caller builds it once per batch and level and hands it to
-// spt_edge_attn_bwd_ex_f32 (which otherwise rebuilds it in its workspace on every call).
-extern "C" int spt_attn_pack_tile_ids(const int32_t* eperm, const int32_t* tgt_sorted,
-                                      const int32_t* src_sorted, int64_t e, int32_t* tile_ids,
-                                      spt_stream_t stream_) {
-  SPT_CHECK_ARG(e >= 0 && (e == 0 || (tgt_sorted && src_sorted && tile_ids)), "null pointer");
-  // the 48-int source-order records: the target-order backward (the default) reads another format
-  // and would silently walk garbage - refuse instead of writing records nobody can use
-  SPT_CHECK_ARG(!attn_bwd_to_enabled(),
-                "the target-order backward is on: build the tile records with spt_attn_pack_tile_ids_ex / "
-                "_m (or switch it off with spt_attn_bwd_el_target_order(0))");
-  attn_pack_tile_ids_launch(eperm, tgt_sorted, src_sorted, e, tile_ids, (hipStream_t)stream_);
-  SPT_CHECK_LAUNCH();
-  return 0;
-}
-
-// Tile records in the format the edge-lane backward of the current process setting reads
-// (spt_attn_bwd_el_target_order): 64 ints per tile in TARGET order when it is on (needs `tperm`,
-// the CSR view of the targets over the CSR positions, and `src_sorted`), else the 48-int
-// source-order records of spt_attn_pack_tile_ids.  spt_attn_tile_record_ints() = ints per tile.
-extern "C" int spt_attn_tile_record_ints(void) { return attn_bwd_to_enabled() ? 64 : 48; }
-extern "C" int spt_attn_tile_record_ints_m(int mode) { return mode_target_order(mode) ? 64 : 48; }
-extern "C" int spt_attn_pack_tile_ids_ex(const int32_t* eperm, const int32_t* tgt_sorted,
-                                         const int32_t* src_sorted, const int32_t* tperm, int64_t e,
-                                         int32_t* tile_ids, spt_stream_t stream_) {
-  return spt_attn_pack_tile_ids_m(eperm, tgt_sorted, src_sorted, tperm, e, -1, tile_ids, stream_);
-}
-// Same with the edge order taken from bits 6-7 of a per-call `mode` word (the word handed to
-// spt_edge_attn_bwd_ex_f32 afterwards): the records' format follows the call, not the process.
-extern "C" int spt_attn_pack_tile_ids_m(const int32_t* eperm, const int32_t* tgt_sorted,
-                                        const int32_t* src_sorted, const int32_t* tperm, int64_t e,
-                                        int mode, int32_t* tile_ids, spt_stream_t stream_) {
-  SPT_CHECK_ARG(e >= 0 && (e == 0 || (tgt_sorted && src_sorted && tile_ids)), "null pointer");
-  if (mode_target_order(mode)) {
-    SPT_CHECK_ARG(e == 0 || tperm, "target-order tile records need the target view (tperm)");
-    attn_pack_tile_ids_to_launch(eperm, tgt_sorted, src_sorted, tperm, e, tile_ids, (hipStream_t)stream_);
-  } else {
-    attn_pack_tile_ids_launch(eperm, tgt_sorted, src_sorted, e, tile_ids, (hipStream_t)stream_);
-  }
-  SPT_CHECK_LAUNCH();
-  return 0;
-}
-
-// Target-order tile records from the MIRROR structure of the edge list instead of a sorted target
-// view (edge_attn_to.hip): `edge_index` = the [2, e] int64 list as the reference hands it over,
-// `pairs` = M with edge i < M mirrored at i + M and every edge from 2 M on a self loop.
-// spt_attn_mirror_prepare writes inv [e] (the inverse of eperm) and ORs into *flag (int32, device;
-// the caller clears it): bit 0 = a pair that is not (s, t) / (t, s), bit 1 = a loop with s != t.
-// spt_attn_pack_tile_ids_mirror then writes the same 64-int records spt_attn_pack_tile_ids_m
-// writes in target order (the edges into a node in another order: sums of the same terms).
-extern "C" int spt_attn_mirror_prepare(const int64_t* edge_index, const int32_t* eperm, int64_t e,
-                                       int64_t pairs, int32_t* inv, int32_t* flag,
-                                       spt_stream_t stream_) {
-  SPT_CHECK_ARG(e >= 0 && pairs >= 0 && 2 * pairs <= e, "bad shape");
-  SPT_CHECK_ARG(e == 0 || (edge_index && eperm && inv && flag), "null pointer");
-  attn_mirror_prepare_launch(edge_index, eperm, e, pairs, inv, flag, (hipStream_t)stream_);
-  SPT_CHECK_LAUNCH();
-  return 0;
-}
-extern "C" int spt_attn_pack_tile_ids_mirror(const int32_t* eperm, const int32_t* tgt_sorted,
-                                             const int32_t* src_sorted, const int32_t* inv,
-                                             int64_t e, int64_t pairs, int32_t* tile_ids,
-                                             spt_stream_t stream_) {
-  SPT_CHECK_ARG(e >= 0 && pairs >= 0 && 2 * pairs <= e, "bad shape");
-  SPT_CHECK_ARG(e == 0 || (eperm && tgt_sorted && src_sorted && inv && tile_ids), "null pointer");
-  attn_pack_tile_ids_mirror_launch(eperm, tgt_sorted, src_sorted, inv, e, pairs, tile_ids,
-                                   (hipStream_t)stream_);
-  SPT_CHECK_LAUNCH();
-  return 0;
-}
-
-// The general entry: `src_sorted` (nullable) = source node of every CSR position (edge_index[0]
-// in CSR order); `tile_ids` (nullable) = spt_attn_pack_tile_ids of the graph; `tperm` / `trowptr`
-// (nullable, both or none) = CSR view of tgt_sorted over the
-// CSR positions (spt_csr_build on tgt_sorted): the edge-lane backward sums dk / dv per target
-// through it instead of scattering them with atomics; `mode` = per-call formulation word (< 0:
-// process defaults).
-extern "C" int spt_edge_attn_bwd_ex_f32(const float* qkv, int64_t n, int H, int D, int Dv,
-                                        const int32_t* erowptr, const int32_t* eperm,
-                                        const int32_t* tgt_sorted, const int32_t* src_sorted,
-                                        const int32_t* tile_ids, const int32_t* tperm,
-                                        const int32_t* trowptr, int64_t e, const float* edge_attr,
-                                        int F, const float* Wk,
-                                        const float* bk, const float* Wq, const float* bq,
-                                        const float* Wv, const float* bv, int scale_mode,
-                                        float scale_a, const float* out, const float* m,
-                                        const float* z, const float* gout, float* gqkv,
-                                        float* gedge_attr, int gedge_attr_accumulate,
-                                        float* gWk, float* gbk, float* gWq, float* gbq,
-                                        float* gWv, float* gbv, int mode, void* ws,
-                                        size_t ws_bytes, spt_stream_t stream_) {
+// The general entry: `src_sorted` (nullable) = edge_index[0] in CSR order; `tile_ids` (nullable) =
+// the graph's tile records in the format of `mode`'s edge order; `tperm` / `trowptr` (nullable, both
+// or none) = CSR view of tgt_sorted over the CSR positions; `mode` = the per-call word.
+// Validate, route, zero gqkv where the route adds into it, one launch per route, reduce the tables.
+extern "C" int spt_edge_attn_bwd_ex_f32(
+    const float* qkv, int64_t n, int H, int D, int Dv, const int32_t* erowptr, const int32_t* eperm,
+    const int32_t* tgt_sorted, const int32_t* src_sorted, const int32_t* tile_ids, const int32_t* tperm,
+    const int32_t* trowptr, int64_t e, const float* edge_attr, int F, const float* Wk, const float* bk,
+    const float* Wq, const float* bq, const float* Wv, const float* bv, int scale_mode, float scale_a,
+    const float* out, const float* m, const float* z, const float* gout, float* gqkv, float* gedge_attr,
+    int gedge_attr_accumulate, float* gWk, float* gbk, float* gWq, float* gbq, float* gWv, float* gbv,
+    int mode, void* ws, size_t ws_bytes, spt_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   const int gea_acc = gedge_attr_accumulate != 0;
-  const int prec = mode_precision(mode);
-  int form = mode_bwd_form(mode);
   SPT_CHECK_ARG(n >= 0 && e >= 0 && H >= 1 && D >= 1 && Dv >= 1, "bad shape");
   if (n == 0) return 0;
   SPT_CHECK_ARG(qkv && erowptr && out && m && z && gout && gqkv && (tgt_sorted || e == 0), "null pointer");
   const bool has_rpe = edge_attr && (Wk || Wq || Wv);
   SPT_CHECK_ARG(!has_rpe || gedge_attr, "gedge_attr is required with RPE");
   if (!edge_attr) F = 32;
-  const int qpl = per_lane(H * D), vpl = per_lane(H * Dv);
   const int ld = 2 * H * D + H * Dv;
   const size_t len = (size_t)ld * (F + 1);
-  const size_t need = attn_tables_bytes(H, D, Dv, F);
-  SPT_CHECK_ARG(!has_rpe || (ws && ws_bytes >= need), "workspace too small");
+  const size_t tables = attn_tables_bytes(H, D, Dv, F);
+  SPT_CHECK_ARG(!has_rpe || (ws && ws_bytes >= tables), "workspace too small");
   float* partial = has_rpe ? (float*)ws : nullptr;
-  const size_t partial_bytes = align_up((size_t)EA_BWD_BLOCKS * EA_WAVES * len * 4, 256);
-  (void)partial_bytes;   // (the reduced table used to live behind the partials: written in place now)
-  const int grid = (int)(ceil_div(n, EA_WAVES) < EA_BWD_BLOCKS ? ceil_div(n, EA_WAVES) : EA_BWD_BLOCKS);
-  // (the target-order route needs either the sorted target view or ready-made tile records -
-  // spt_attn_pack_tile_ids_mirror builds them without a view; the source-order route needs the view)
-  const bool el_ok = form == 2 && prec >= 2 && e > 0 &&
-                     (tperm || (mode_target_order(mode) && tile_ids && src_sorted)) &&
-                     attn_mfma_shape_ok(H, D, Dv, F, edge_attr, Wk, Wq, Wv);
-  // The edge-lane route is decided ONCE, from the mode word and from what the caller handed over;
-  // each edge order has its own scratch layout, and a route only runs inside the bytes it needs
-  // (spt_edge_attn_bwd_ex_workspace_bytes covers both).
-  const bool to_sel = mode_target_order(mode);
-  const size_t need_el = need + attn_bwd_el_workspace_bytes(n, e);
-  const size_t need_to = need + attn_bwd_to_workspace_bytes(n, e);
-  const bool run_to = el_ok && to_sel && src_sorted && ws_bytes >= need_to;
-  const bool run_el = el_ok && !run_to && tperm && ws_bytes >= need_el;
-  // records built for the target order (64 ints) must not reach the source-order kernel (48 ints):
-  // when the call falls back from the selected target order, the ids are rebuilt in the workspace
-  if (run_el && to_sel) tile_ids = nullptr;
-  // gqkv receives atomics: start from zero (the edge-lane paths initialise it themselves)
-  if (!(run_to || run_el)) hipMemsetAsync(gqkv, 0, (size_t)n * ld * 4, stream);
-  if (prec != 0 && attn_mfma_shape_ok(H, D, Dv, F, edge_attr, Wk, Wq, Wv)) {
-    int ntab;
-    if (form == 2 && mode >= 0 && ((mode >> 4) & 3) == 3)
-      SPT_CHECK_ARG((run_to && (trowptr || tile_ids)) || (run_el && trowptr),
-                    "edge-lane backward: workspace of spt_edge_attn_bwd_ex_workspace_bytes, the "
-                    "target CSR view (or target-order tile records) and a bf16-pipe precision are required");
-    if (mode >= 0 && ((mode >> 6) & 3) == 1 && el_ok)
-      SPT_CHECK_ARG(run_to, "target-order backward: src_sorted and the workspace of "
-                            "spt_edge_attn_bwd_ex_workspace_bytes are required");
+  const int word = spt_attn_resolve_mode(mode);
+  const int kprec = attn_kernel_prec(attn_mode_precision(word));
+  const int operands = (edge_attr && Wk && Wq && Wv ? SPT_ATTN_HAS_RPE : 0) | (src_sorted ? SPT_ATTN_HAS_SRC : 0) |
+                       (tile_ids ? SPT_ATTN_HAS_TILE_IDS : 0) | (tperm ? SPT_ATTN_HAS_TARGET_VIEW : 0);
+  const char* why = nullptr;
+  const int route = attn_bwd_route(n, e, H, D, Dv, F, operands, word, ws_bytes, &why);
+  if (route < 0) return attn_refuse(__func__, route, why, H, D, Dv, F);
+  if (route != SPT_ATTN_ROUTE_VALU)
     SPT_CHECK_ARG((tperm == nullptr) == (trowptr == nullptr), "pass both tperm and trowptr or neither");
-    if (run_to) {
-      // edge stream in target order (edge_attn_to.hip); `tile_ids`, when given, are the 64-int
-      // records of spt_attn_pack_tile_ids_ex
+  // gqkv receives atomics: start from zero (the edge-lane routes initialise it themselves)
+  if (route != SPT_ATTN_ROUTE_EDGE_LANE_TARGET && route != SPT_ATTN_ROUTE_EDGE_LANE_SOURCE)
+    (void)hipMemsetAsync(gqkv, 0, (size_t)n * ld * 4, stream);
+  int ntab;  // partial weight-gradient tables written
+  switch (route) {
+    case SPT_ATTN_ROUTE_EDGE_LANE_TARGET:
       ntab = attn_bwd_to_launch(qkv, n, erowptr, eperm, tgt_sorted, src_sorted, tile_ids, tperm, e,
                                 edge_attr, Wk, bk, Wq, bq, Wv, bv, scale_mode, scale_a, out, m, z,
-                                gout, gqkv, gedge_attr, gea_acc, partial, (char*)ws + need,
-                                prec == 2 ? 3 : 1, stream);
-    } else if (run_el) {
-      ntab = attn_bwd_el_launch(qkv, n, erowptr, eperm, tgt_sorted, src_sorted, tile_ids, tperm,
-                                trowptr, e, edge_attr, Wk,
-                                bk, Wq, bq, Wv, bv, scale_mode, scale_a, out, m, z, gout, gqkv,
-                                gedge_attr, gea_acc, partial, (char*)ws + need, prec == 2 ? 3 : 1,
-                                stream);
-    } else {
-      ntab = attn_bwd_mfma_launch(qkv, n, erowptr, eperm, tgt_sorted, edge_attr, Wk, bk,
-                                  Wq, bq, Wv, bv, scale_mode, scale_a, out, m, z, gout,
-                                  gqkv, gedge_attr, gea_acc, partial,
-                                  prec == 2 ? 3 : (prec == 3 ? 1 : 0), e, form != 0, stream);
+                                gout, gqkv, gedge_attr, gea_acc, partial, (char*)ws + tables, kprec, stream);
+      break;
+    case SPT_ATTN_ROUTE_EDGE_LANE_SOURCE:
+      // records built for the target order (64 ints) must not reach this kernel (48 ints): a call
+      // that fell back from the target order rebuilds them in the workspace
+      if (attn_mode_target_order(word)) tile_ids = nullptr;
+      ntab = attn_bwd_el_launch(qkv, n, erowptr, eperm, tgt_sorted, src_sorted, tile_ids, tperm, trowptr,
+                                e, edge_attr, Wk, bk, Wq, bq, Wv, bv, scale_mode, scale_a, out, m, z,
+                                gout, gqkv, gedge_attr, gea_acc, partial, (char*)ws + tables, kprec, stream);
+      break;
+    case SPT_ATTN_ROUTE_PACKED:
+    case SPT_ATTN_ROUTE_PER_NODE:
+      ntab = attn_bwd_mfma_launch(qkv, n, erowptr, eperm, tgt_sorted, edge_attr, Wk, bk, Wq, bq, Wv, bv,
+                                  scale_mode, scale_a, out, m, z, gout, gqkv, gedge_attr, gea_acc,
+                                  partial, kprec, e, route == SPT_ATTN_ROUTE_PACKED, stream);
+      break;
+    default: {  // SPT_ATTN_ROUTE_VALU
+      const int grid = (int)(ceil_div(n, EA_WAVES) < EA_BWD_BLOCKS ? ceil_div(n, EA_WAVES) : EA_BWD_BLOCKS);
+      attn_valu_case(H, D, Dv, F, [&](const AttnShape& sh, auto c) {
+        using C = decltype(c);
+        edge_attn_bwd_kernel<C::q, C::v, C::f><<<grid, EA_WAVES * 64, 0, stream>>>(
+            qkv, ld, n, sh, erowptr, eperm, tgt_sorted, edge_attr, Wk, bk, Wq, bq, Wv, bv,
+            scale_mode, scale_a, out, m, z, gout, gqkv, gedge_attr, partial, gea_acc);
+      });
+      ntab = grid * EA_WAVES;
     }
+  }
+  if (has_rpe)
     attn_reduce_partials_kernel<<<(int)ceil_div((int64_t)len, 16), 256, 0, stream>>>(
         partial, ntab, (int)len, H * D, H * Dv, F, gWk, gbk, gWq, gbq, gWv, gbv);
-    SPT_CHECK_LAUNCH();
-    return 0;
-  }
-#define SPT_ATTN_CASE(FN, Q, V, FF, ...)                                        \
-  if (!done__ && qpl == Q && vpl == V && F == FF) {                            \
-    AttnShape sh;                                                              \
-    if (attn_shape(H, D, Dv, Q, V, &sh)) {                                     \
-      FN<Q, V, FF><<<grid, EA_WAVES * 64, 0, stream>>>(__VA_ARGS__);           \
-      done__ = true;                                                           \
-    }                                                                          \
-  }
-  SPT_ATTN_DISPATCH(edge_attn_bwd_kernel, qkv, ld, n, sh, erowptr, eperm, tgt_sorted,
-                    edge_attr, Wk, bk, Wq, bq, Wv, bv, scale_mode, scale_a, out, m, z,
-                    gout, gqkv, gedge_attr, partial, gea_acc);
-#undef SPT_ATTN_CASE
-  if (has_rpe) {
-    attn_reduce_partials_kernel<<<(int)ceil_div((int64_t)len, 16), 256, 0, stream>>>(
-        partial, grid * EA_WAVES, (int)len, H * D, H * Dv, F, gWk, gbk, gWq, gbq, gWv, gbv);
-  }
   SPT_CHECK_LAUNCH();
   return 0;
 }

@@ -48,6 +48,7 @@
 #include <stdlib.h>
 
 #include "common.hpp"
+#include "edge_attn_internal.hpp"
 
 namespace spt {
 namespace el {

@@ -22,6 +22,7 @@
 #include <math.h>
 
 #include "common.hpp"
+#include "edge_attn_internal.hpp"
 
 namespace spt {
 namespace mfma {
@@ -1513,10 +1514,8 @@ SPT_PROBE(6)
 }  // namespace mfma
 
 // ---- launchers called from edge_attn.hip's C entry points --------------------
-bool attn_xcd_bands();      // edge_attn.hip: SPT_ATTN_XCD_BANDS (default on)
-bool attn_mfma_shape_ok(int H, int D, int Dv, int F, const void* ea, const void* Wk,
-                        const void* Wq, const void* Wv) {
-  return H == 16 && D == 4 && Dv == 4 && F == 32 && ea && Wk && Wq && Wv;
+bool attn_mfma_shape_ok(int H, int D, int Dv, int F, bool has_rpe) {
+  return H == 16 && D == 4 && Dv == 4 && F == 32 && has_rpe;
 }
 
 void attn_fwd_mfma_launch(const float* qkv, int64_t n, const int32_t* erowptr,

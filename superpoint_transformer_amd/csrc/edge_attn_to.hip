@@ -25,6 +25,7 @@
 #include <stdlib.h>
 
 #include "common.hpp"
+#include "edge_attn_internal.hpp"
 
 namespace spt {
 namespace to {
@@ -896,16 +897,6 @@ __global__ __launch_bounds__(WAVES * 64, 2) void attn_bwd_to_kernel(
 // ---- launcher called from edge_attn.hip's C entry points ------------------------------------
 constexpr int ATTN_TO_MAX_PAIRS = 1024;     // 256 workgroups of 4 pairs: one workgroup per CU
 
-// edge order of the edge-lane backward: 1 = by TARGET (this file; default), 0 = by source
-// (edge_attn_el.hip).  Process-wide measurement / fallback switch.
-static std::atomic<int> g_attn_el_target_order{[] { const char* e = getenv("SPT_EL_TARGET_ORDER"); return e ? (atoi(e) != 0) : 1; }()};
-extern "C" int spt_attn_bwd_el_target_order(int on) {
-  const int prev = g_attn_el_target_order;
-  if (on >= 0) g_attn_el_target_order = on != 0;
-  return prev;
-}
-bool attn_bwd_to_enabled() { return g_attn_el_target_order != 0; }
-
 size_t attn_bwd_to_workspace_bytes(int64_t n, int64_t e) {
   const size_t ee = (size_t)(e > 0 ? e : 1);
   const size_t ntiles = (ee + to::TE - 1) / to::TE;
@@ -921,7 +912,6 @@ void attn_pack_tile_ids_to_launch(const int32_t* eperm, const int32_t* tgt, cons
         eperm, tgt, src, tperm, e, ntiles, ids4);
 }
 
-bool attn_xcd_bands();      // edge_attn.hip: SPT_ATTN_XCD_BANDS (default on)
 int attn_mirror_prepare_launch(const int64_t* ei, const int32_t* eperm, int64_t e, int64_t pairs,
                                int32_t* inv, int32_t* flag, hipStream_t stream) {
   if (e > 0)

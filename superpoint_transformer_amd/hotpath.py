@@ -84,12 +84,35 @@ def _pmc_traffic(op, workload):
         return None
 
 
-def _kernel_names(mode):
+def _attn_bwd_kernels(level1):
+    """Kernels of one level-1 attention backward (SPT-64 head layout, ``level1`` = (nodes, edges)) in
+    the mode active now: the library's own route for that call (spt_edge_attn_bwd_route, asked the
+    way ops._attn_bwd_plan asks it) looked up in a table of what each route launches."""
+    from . import ops, precision
+    word = _lib.lib.spt_attn_resolve_mode(precision.attention_mode())
+    p = {0: None, 1: 0, 2: 3, 3: 1}[word & 3]              # the matrix-pipe kernels' PREC parameter
+    reduce = " + spt::attn_reduce_partials_kernel"
+    kernels = {
+        ops.ATTN_ROUTE_VALU: "hipMemsetAsync + spt::edge_attn_bwd_kernel<1, 1, 32>" + reduce,
+        ops.ATTN_ROUTE_PER_NODE: f"hipMemsetAsync + spt::mfma::attn_bwd_mfma_kernel<{p}>"
+                                 + (" (f32 matrix pipe)" if p == 0 else "") + reduce,
+        ops.ATTN_ROUTE_PACKED: f"hipMemsetAsync + spt::mfma::attn_bwd_packed_kernel<{p}>" + reduce,
+        ops.ATTN_ROUTE_EDGE_LANE_SOURCE: f"spt::el::attn_bwd_prep_kernel + spt::el::attn_bwd_el_kernel<{p}> + "
+                                         "spt::el::attn_kv_reduce_kernel" + reduce,
+        ops.ATTN_ROUTE_EDGE_LANE_TARGET: f"spt::to::attn_bwd_to_prep_kernel + spt::to::attn_bwd_to_kernel<{p}> + "
+                                         "spt::to::attn_q_reduce_kernel" + reduce,
+    }
+    n1, e1 = level1
+    route = _lib.lib.spt_edge_attn_bwd_route(n1, e1, 16, 4, 4, 32, 1 | 2 | 4 | 8, word, 1 << 62)
+    _lib.check(min(route, 0), "spt_edge_attn_bwd_route")
+    return kernels[route]
+
+
+def _kernel_names(mode, level1):
     """Kernels behind the four timed ops in matrix mode ``mode`` (precision.get_matrix_precision):
-    what the dispatch of csrc/edge_attn.hip / fused_mlp.hip launches for the SPT-64 head layout."""
+    what csrc/edge_attn.hip / fused_mlp.hip launch for the SPT-64 head layout."""
     if mode == "f32-exact":
-        return {"attn_bwd": "hipMemsetAsync + spt::mfma::attn_bwd_packed_kernel<0> (f32 matrix pipe) + "
-                            "spt::attn_reduce_partials_kernel",
+        return {"attn_bwd": _attn_bwd_kernels(level1),
                 "attn_fwd": "spt::mfma::attn_fwd_mfma_kernel<0> (f32 matrix pipe)",
                 "mlp_bwd_pooled": None,        # mode 0 has no pooled backward: dense route
                 "mlp_fwd": "spt::fmlp::fwd_kernel<16, 8> (f32 matrix pipe)"}
@@ -97,11 +120,7 @@ def _kernel_names(mode):
     lo = "true" if mode == "f32" else "false"
     from . import precision
     st = mode == "bf16" and precision.bf16_activation_storage()   # layer outputs stored as bf16
-    to = bool(_lib.lib.spt_attn_bwd_el_target_order(-1))           # edge stream by target / by source
-    return {"attn_bwd": (f"spt::to::attn_bwd_to_prep_kernel + spt::to::attn_bwd_to_kernel<{p}> + "
-                         "spt::to::attn_q_reduce_kernel + spt::attn_reduce_partials_kernel" if to else
-                         f"spt::el::attn_bwd_prep_kernel + spt::el::attn_bwd_el_kernel<{p}> + "
-                         "spt::el::attn_kv_reduce_kernel + spt::attn_reduce_partials_kernel"),
+    return {"attn_bwd": _attn_bwd_kernels(level1),
             "attn_fwd": f"spt::mfma::attn_fwd_mfma_kernel<{p}>",
             "mlp_bwd_pooled": f"spt::fdma::bwd_dma_kernel<64, 128, 8, 2, {lo}, true" + (", true>" if st else ">"),
             "mlp_fwd_pool": (f"spt::fpool::fwd_pool_kernel<64, 128, {3 if mode == 'f32' else 1}, "
@@ -388,7 +407,7 @@ class SPTTrainStep:
         kernels = []
         if getattr(self, "k_timers", None):
             n1, e1 = self.level1
-            names = _kernel_names(precision.get_matrix_precision())
+            names = _kernel_names(precision.get_matrix_precision(), self.level1)
             ab = 2 if (precision.get_matrix_precision() == "bf16"
                        and precision.bf16_activation_storage()) else 4
             rows = n0

@@ -553,10 +553,90 @@ class EdgeAttrGradShare:
         return self.count - 1
 
 
+# operand bits and results of spt_edge_attn_bwd_route (include/spt_hip.h)
+_ATTN_HAS_RPE, _ATTN_HAS_SRC, _ATTN_HAS_TILE_IDS, _ATTN_HAS_TARGET_VIEW = 1, 2, 4, 8
+(ATTN_ROUTE_VALU, ATTN_ROUTE_PER_NODE, ATTN_ROUTE_PACKED, ATTN_ROUTE_EDGE_LANE_SOURCE,
+ ATTN_ROUTE_EDGE_LANE_TARGET) = range(5)
+
+
+def _attn_mode(mode=None):
+    """The mode word of one ``edge_attention`` call, every field explicit: resolved ONCE, then
+    handed to the forward, the tile records and (``ctx.mode``) the backward."""
+    return int(_lib.lib.spt_attn_resolve_mode(_precision.attention_mode())) if mode is None else mode
+
+
+def _attn_bwd_plan(ecsr, n, H, D, Dv, F, has_rpe, mode):
+    """(route, workspace, src, tile_ids, tperm, trowptr) of an attention backward in the resolved
+    ``mode``: the library names the route it takes when given everything (spt_edge_attn_bwd_route),
+    that route's operands are prepared, and the route is asked for again with exactly these - a
+    different answer would be a silent downgrade, and raises."""
+    L, dev = _lib.lib, ecsr.tgt_sorted.device
+
+    def route(operands, nbytes):
+        r = L.spt_edge_attn_bwd_route(n, ecsr.e, H, D, Dv, F, operands, mode, nbytes)
+        _lib.check(min(r, 0), "spt_edge_attn_bwd_route")
+        return r
+
+    operands = _ATTN_HAS_RPE if has_rpe else 0
+    want = route(operands | _ATTN_HAS_SRC | _ATTN_HAS_TILE_IDS | _ATTN_HAS_TARGET_VIEW, 1 << 62)
+    src = tids = tperm = trowptr = None
+    if want in (ATTN_ROUTE_EDGE_LANE_SOURCE, ATTN_ROUTE_EDGE_LANE_TARGET):
+        # the larger scratch is asked for only where it is used (the buffer is grow-only)
+        nb = L.spt_edge_attn_bwd_ex_workspace_bytes(n, ecsr.e, H, D, Dv, F)
+        src, tids = ecsr.src_sorted(), ecsr.tile_ids(mode)
+        operands |= _ATTN_HAS_SRC | _ATTN_HAS_TILE_IDS
+        if not ecsr.mirrored(mode):
+            # (a mirrored edge list's target-order records need no sorted target view)
+            tv = ecsr.target_view()
+            tperm, trowptr = tv.perm, tv.rowptr
+            operands |= _ATTN_HAS_TARGET_VIEW
+    else:
+        nb = L.spt_edge_attn_bwd_workspace_bytes(H, D, Dv, max(F, 1))
+    ws = _workspace(nb, dev)
+    got = route(operands, ws.numel())
+    if got != want:
+        raise RuntimeError(f"attention backward (n={n} e={ecsr.e} mode={mode:#x}): prepared for route {want}, "
+                           f"the library would take {got}")
+    return got, ws, src, tids, tperm, trowptr
+
+
+def _attn_fwd_call(q, n, H, D, Dv, ecsr, ea, F, ps, scale_mode, scale_a, out, m, z, mode, dev):
+    """One spt_edge_attn_fwd_ex_f32; ``ps`` = [Wk, bk, Wq, bq, Wv, bv] (None where absent)."""
+    with _timed(f"edge_attn_fwd:{n}:{ecsr.e}"):
+        st = _lib.lib.spt_edge_attn_fwd_ex_f32(
+            _lib.ptr(q), n, H, D, Dv, _lib.ptr(ecsr.erowptr), _lib.ptr(ecsr.eperm),
+            _lib.ptr(ecsr.tgt_sorted), ecsr.e, _lib.ptr(ea), F,
+            *[_lib.ptr(t) for t in ps], scale_mode, scale_a, _lib.ptr(out),
+            _lib.ptr(m), _lib.ptr(z), mode, _lib.stream_ptr(dev))
+    _lib.check(st, "spt_edge_attn_fwd_ex_f32")
+
+
+def _attn_bwd_call(q, n, H, D, Dv, ecsr, plan, ea, F, ps, scale_mode, scale_a, out, m, z, g, gq, gea,
+                   acc, gps, mode, dev, share):
+    """One spt_edge_attn_bwd_ex_f32 with the operands of ``plan`` (_attn_bwd_plan); ``gps`` = the
+    gradients of ``ps`` in the same order."""
+    _, ws, src, tids, tperm, trowptr = plan
+    with _timed(f"edge_attn_bwd:{n}:{ecsr.e}"):
+        st = _lib.lib.spt_edge_attn_bwd_ex_f32(
+            _lib.ptr(q), n, H, D, Dv, _lib.ptr(ecsr.erowptr), _lib.ptr(ecsr.eperm),
+            _lib.ptr(ecsr.tgt_sorted), _lib.ptr(src), _lib.ptr(tids), _lib.ptr(tperm),
+            _lib.ptr(trowptr), ecsr.e, _lib.ptr(ea), F,
+            *[_lib.ptr(t) for t in ps], scale_mode, scale_a, _lib.ptr(out),
+            _lib.ptr(m), _lib.ptr(z), _lib.ptr(g), _lib.ptr(gq), _lib.ptr(gea), acc,
+            *[_lib.ptr(t) for t in gps], mode, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+    if st != 0 and share is not None:
+        share.abort()                                # never leave a half-built sum behind
+    _lib.check(st, "spt_edge_attn_bwd_ex_f32")
+
+
+def _at(t, i):
+    return None if t is None else t[i]
+
+
 class _EdgeAttention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, ecsr, edge_attr, Wk, bk, Wq, bq, Wv, bv, H, D, scale_mode, scale_a,
-                share=None):
+                share=None, mode=None):
         _lib.require_cuda(qkv)
         q2 = _f32c(qkv)
         n, ld = q2.shape
@@ -572,15 +652,9 @@ class _EdgeAttention(torch.autograd.Function):
         out = torch.empty((n, H * Dv), dtype=torch.float32, device=dev)
         m = torch.empty((n, H), dtype=torch.float32, device=dev)
         z = torch.empty((n, H), dtype=torch.float32, device=dev)
-        mode = _precision.attention_mode()       # per call; the backward runs in the same mode
-        with torch.cuda.device(dev), _timed(f"edge_attn_fwd:{n}:{ecsr.e}"):
-            st = _lib.lib.spt_edge_attn_fwd_ex_f32(
-                _lib.ptr(q2), n, H, D, Dv, _lib.ptr(ecsr.erowptr), _lib.ptr(ecsr.eperm),
-                _lib.ptr(ecsr.tgt_sorted), ecsr.e, _lib.ptr(ea), F,
-                *[_lib.ptr(t) for t in ps], scale_mode, scale_a, _lib.ptr(out),
-                _lib.ptr(m), _lib.ptr(z), mode, _lib.stream_ptr(dev))
-        _lib.check(st, "spt_edge_attn_fwd_ex_f32")
-        ctx.mode = mode
+        ctx.mode = mode = _attn_mode(mode)       # resolved: the backward runs in the same mode
+        with torch.cuda.device(dev):
+            _attn_fwd_call(q2, n, H, D, Dv, ecsr, ea, F, ps, scale_mode, scale_a, out, m, z, mode, dev)
         ctx.save_for_backward(q2, ea, *[t for t in ps if t is not None], out, m, z)
         ctx.present = [t is not None for t in ps]
         ctx.has_ea = ea is not None
@@ -612,41 +686,16 @@ class _EdgeAttention(torch.autograd.Function):
         else:
             gea = torch.empty_like(ea) if ea is not None else None
         gps = [torch.empty_like(t) if t is not None else None for t in ps]
-        # the edge-lane formulation needs 512 B per edge + ~390 B per node of scratch on top of the
-        # weight-gradient tables: asked for only when that formulation will run (the scratch
-        # buffer is grow-only per device and stream)
-        el = bool(ea is not None and ecsr.e > 0
-                  and _lib.lib.spt_edge_attn_bwd_el_supported(H, D, Dv, F, ctx.mode))
-        nb = (_lib.lib.spt_edge_attn_bwd_ex_workspace_bytes(n, ecsr.e, H, D, Dv, max(F, 1)) if el
-              else _lib.lib.spt_edge_attn_bwd_workspace_bytes(H, D, Dv, max(F, 1)))
-        ws = _workspace(nb, dev)
-        src = tids = tperm = trowptr = None
-        if el:
-            src = ecsr.src_sorted()
-            tids = ecsr.tile_ids(ctx.mode)
-            if not ecsr.mirrored(ctx.mode):
-                # (a mirrored edge list's target-order records need no sorted target view)
-                tv = ecsr.target_view()
-                tperm, trowptr = tv.perm, tv.rowptr
-        with torch.cuda.device(dev), _timed(f"edge_attn_bwd:{n}:{ecsr.e}"):
-            st = _lib.lib.spt_edge_attn_bwd_ex_f32(
-                _lib.ptr(q2), n, H, D, Dv, _lib.ptr(ecsr.erowptr), _lib.ptr(ecsr.eperm),
-                _lib.ptr(ecsr.tgt_sorted), _lib.ptr(src), _lib.ptr(tids), _lib.ptr(tperm),
-                _lib.ptr(trowptr),
-                ecsr.e, _lib.ptr(ea), F,
-                *[_lib.ptr(t) for t in ps], scale_mode, scale_a, _lib.ptr(out),
-                _lib.ptr(m), _lib.ptr(z), _lib.ptr(g), _lib.ptr(gqkv), _lib.ptr(gea), acc,
-                *[_lib.ptr(t) for t in gps], ctx.mode, _lib.ptr(ws), ws.numel(),
-                _lib.stream_ptr(dev))
-        if st != 0 and share is not None:
-            share.abort()                                # never leave a half-built sum behind
-        _lib.check(st, "spt_edge_attn_bwd_ex_f32")
+        plan = _attn_bwd_plan(ecsr, n, H, D, Dv, F, ea is not None and all(ctx.present[0::2]), ctx.mode)
+        with torch.cuda.device(dev):
+            _attn_bwd_call(q2, n, H, D, Dv, ecsr, plan, ea, F, ps, scale_mode, scale_a, out, m, z, g,
+                           gqkv, gea, acc, gps, ctx.mode, dev, share)
         if gea is not None and not (any(ctx.present[0::2])):
             gea = None
         if share is not None:
             gea = share.release(ctx.rank)                # the first block returns the sum
         return (gqkv.to(q_dtype), None, None if gea is None else gea.to(ea_dtype),
-                *gps, None, None, None, None, None)
+                *gps, None, None, None, None, None, None)
 
 
 def edge_attention(qkv, edge_index, edge_attr=None, k_rpe=None, q_rpe=None, v_rpe=None,
@@ -668,23 +717,24 @@ def edge_attention(qkv, edge_index, edge_attr=None, k_rpe=None, q_rpe=None, v_rp
     Wv, bv = wb(v_rpe)
     H, D = int(num_heads), int(qk_dim)
     share = ea_grad if torch.is_grad_enabled() else None
-    split = _matrix_pipe_split(qkv, edge_attr, Wk, Wq, Wv, H, D)
+    mode = _attn_mode()                  # resolved once: everything below runs in this word
+    split = _matrix_pipe_split(qkv, edge_attr, Wk, Wq, Wv, H, D, mode)
     if split is None:
-        padded = _matrix_pipe_pad(qkv, ecsr, edge_attr, Wk, bk, Wq, bq, Wv, bv, H, D)
+        padded = _matrix_pipe_pad(qkv, ecsr, edge_attr, Wk, bk, Wq, bq, Wv, bv, H, D, mode)
         if padded is not None:
             # narrower head layouts (nano: 16 heads of qk_dim 2, value dim 1, 16-D edge encodings)
             # zero-padded to the built (16, 4, 4, 32) shape: the matrix-pipe kernels instead of
             # the generic VALU ones; plain torch ops do the padding, autograd their backward
             qp, eap, wk, bkp, wq, bqp, wv, bvp, dv = padded
             out = _EdgeAttention.apply(qp, ecsr, eap, wk, bkp, wq, bqp, wv, bvp, 16, 4,
-                                       int(scale_mode), float(scale_a), None)
+                                       int(scale_mode), float(scale_a), None, mode)
             return out.view(out.shape[0], 16, 4)[:, :, :dv].reshape(out.shape[0], 16 * dv)
         return _EdgeAttention.apply(qkv, ecsr, edge_attr, Wk, bk, Wq, bq, Wv, bv, H, D,
-                                    int(scale_mode), float(scale_a), share)
+                                    int(scale_mode), float(scale_a), share, mode)
     # wider head layouts (SPT-128: 16 heads of value dim 8; 32 heads) on the matrix-pipe kernels
     G, J, _ = split
     return _EdgeAttentionSplit.apply(qkv, ecsr, edge_attr, Wk, bk, Wq, bq, Wv, bv, H, G, J,
-                                     int(scale_mode), float(scale_a), share)
+                                     int(scale_mode), float(scale_a), share, mode)
 
 
 class _EdgeAttentionSplit(torch.autograd.Function):
@@ -723,7 +773,7 @@ class _EdgeAttentionSplit(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, ecsr, edge_attr, Wk, bk, Wq, bq, Wv, bv, H, G, J, scale_mode, scale_a,
-                share=None):
+                share=None, mode=None):
         _lib.require_cuda(qkv)
         q2 = _f32c(qkv)
         n = q2.shape[0]
@@ -743,23 +793,15 @@ class _EdgeAttentionSplit(torch.autograd.Function):
         oa = torch.empty((P, n, 64), dtype=torch.float32, device=dev)
         m = torch.empty((P, n, 16), dtype=torch.float32, device=dev)
         z = torch.empty((P, n, 16), dtype=torch.float32, device=dev)
-        mode = _precision.attention_mode()
+        ctx.mode = mode = _attn_mode(mode)
         with torch.cuda.device(dev):
             for gi in range(G):
                 cs = slice(64 * gi, 64 * gi + 64)
                 for j in range(J):
                     p = gi * J + j
-                    with _timed(f"edge_attn_fwd:{n}:{ecsr.e}"):
-                        st = _lib.lib.spt_edge_attn_fwd_ex_f32(
-                            _lib.ptr(qa[p]), n, 16, 4, 4, _lib.ptr(ecsr.erowptr), _lib.ptr(ecsr.eperm),
-                            _lib.ptr(ecsr.tgt_sorted), ecsr.e, _lib.ptr(ea), F,
-                            _lib.ptr(Wk2[cs]), _lib.ptr(None if bk2 is None else bk2[cs]),
-                            _lib.ptr(Wq2[cs]), _lib.ptr(None if bq2 is None else bq2[cs]),
-                            _lib.ptr(Wva[gi, j]), _lib.ptr(None if bva is None else bva[gi, j]),
-                            scale_mode, scale_a, _lib.ptr(oa[p]), _lib.ptr(m[p]), _lib.ptr(z[p]),
-                            mode, _lib.stream_ptr(dev))
-                    _lib.check(st, "spt_edge_attn_fwd_ex_f32")
-        ctx.mode = mode
+                    ps = [Wk2[cs], _at(bk2, cs), Wq2[cs], _at(bq2, cs), Wva[gi, j], _at(bva, (gi, j))]
+                    _attn_fwd_call(qa[p], n, 16, 4, 4, ecsr, ea, F, ps, scale_mode, scale_a, oa[p], m[p],
+                                   z[p], mode, dev)
         ctx.save_for_backward(qa, ea, Wk2, Wq2, Wva, oa, m, z,
                               *[t for t in (bk2, bq2, bva) if t is not None])
         ctx.has_b = [t is not None for t in (bk2, bq2, bva)]
@@ -792,38 +834,16 @@ class _EdgeAttentionSplit(torch.autograd.Function):
         gbk = torch.empty((P, 64), dtype=torch.float32, device=dev) if bk2 is not None else None
         gbq = torch.empty((P, 64), dtype=torch.float32, device=dev) if bq2 is not None else None
         gbv = torch.empty((P, 64), dtype=torch.float32, device=dev) if bva is not None else None
-        el = bool(ecsr.e > 0 and _lib.lib.spt_edge_attn_bwd_el_supported(16, 4, 4, F, ctx.mode))
-        nb = (_lib.lib.spt_edge_attn_bwd_ex_workspace_bytes(n, ecsr.e, 16, 4, 4, F) if el
-              else _lib.lib.spt_edge_attn_bwd_workspace_bytes(16, 4, 4, F))
-        ws = _workspace(nb, dev)
-        src = tids = tperm = trowptr = None
-        if el:
-            src, tids = ecsr.src_sorted(), ecsr.tile_ids(ctx.mode)
-            if not ecsr.mirrored(ctx.mode):
-                tv = ecsr.target_view()
-                tperm, trowptr = tv.perm, tv.rowptr
+        plan = _attn_bwd_plan(ecsr, n, 16, 4, 4, F, True, ctx.mode)
         with torch.cuda.device(dev):
             for gi in range(G):
                 cs = slice(64 * gi, 64 * gi + 64)
                 for j in range(J):
                     p = gi * J + j
-                    with _timed(f"edge_attn_bwd:{n}:{ecsr.e}"):
-                        st = _lib.lib.spt_edge_attn_bwd_ex_f32(
-                            _lib.ptr(qa[p]), n, 16, 4, 4, _lib.ptr(ecsr.erowptr), _lib.ptr(ecsr.eperm),
-                            _lib.ptr(ecsr.tgt_sorted), _lib.ptr(src), _lib.ptr(tids), _lib.ptr(tperm),
-                            _lib.ptr(trowptr), ecsr.e, _lib.ptr(ea), F,
-                            _lib.ptr(Wk2[cs]), _lib.ptr(None if bk2 is None else bk2[cs]),
-                            _lib.ptr(Wq2[cs]), _lib.ptr(None if bq2 is None else bq2[cs]),
-                            _lib.ptr(Wva[gi, j]), _lib.ptr(None if bva is None else bva[gi, j]),
-                            scale_mode, scale_a, _lib.ptr(oa[p]), _lib.ptr(m[p]), _lib.ptr(z[p]),
-                            _lib.ptr(ga[p]), _lib.ptr(gqa[p]), _lib.ptr(gea), acc,
-                            _lib.ptr(gWk[p]), _lib.ptr(None if gbk is None else gbk[p]),
-                            _lib.ptr(gWq[p]), _lib.ptr(None if gbq is None else gbq[p]),
-                            _lib.ptr(gWv[p]), _lib.ptr(None if gbv is None else gbv[p]),
-                            ctx.mode, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-                    if st != 0 and share is not None:
-                        share.abort()
-                    _lib.check(st, "spt_edge_attn_bwd_ex_f32")
+                    ps = [Wk2[cs], _at(bk2, cs), Wq2[cs], _at(bq2, cs), Wva[gi, j], _at(bva, (gi, j))]
+                    gps = [gWk[p], _at(gbk, p), gWq[p], _at(gbq, p), gWv[p], _at(gbv, p)]
+                    _attn_bwd_call(qa[p], n, 16, 4, 4, ecsr, plan, ea, F, ps, scale_mode, scale_a, oa[p],
+                                   m[p], z[p], ga[p], gqa[p], gea, acc, gps, ctx.mode, dev, share)
                     acc = 1
         # q / k (and their encoders') gradients: the sum over a head group's J value slices
         gqkv = torch.empty((n, 2 * QK + H * Dv), dtype=torch.float32, device=dev)
@@ -847,7 +867,7 @@ class _EdgeAttentionSplit(torch.autograd.Function):
             gea = share.release(ctx.rank)
         return (gqkv.to(q_dtype), None, None if gea is None else gea.to(ea_dtype),
                 over_j(gWk, (64, F)), over_j(gbk, (64,)), over_j(gWq, (64, F)), over_j(gbq, (64,)),
-                value_rows(gWv, (F,)), value_rows(gbv, ()), None, None, None, None, None, None)
+                value_rows(gWv, (F,)), value_rows(gbv, ()), None, None, None, None, None, None, None)
 
 
 _SPLIT_COLS = {}
@@ -856,7 +876,7 @@ _SPLIT_COLS = {}
 PAD_MIN_EDGES = 1 << 16        # below that the generic kernels are a few microseconds anyway
 
 
-def _matrix_pipe_pad(qkv, ecsr, edge_attr, Wk, bk, Wq, bq, Wv, bv, H, D):
+def _matrix_pipe_pad(qkv, ecsr, edge_attr, Wk, bk, Wq, bq, Wv, bv, H, D, mode=None):
     """Operands of a head layout NARROWER than the built (16, 4, 4, 32) one, zero-padded to it
     (H = 16, qk_dim <= 4, value dim <= 4, in_rpe_dim <= 32, all three RPE encoders, a
     matrix-pipe precision active, enough edges to matter); None otherwise.  Exact: padded q / k
@@ -873,10 +893,7 @@ def _matrix_pipe_pad(qkv, ecsr, edge_attr, Wk, bk, Wq, bq, Wv, bv, H, D):
         return None
     if qkv.dtype != torch.float32 or edge_attr.dtype != torch.float32:
         return None
-    mode = _precision.attention_mode()
-    if mode < 0:
-        mode = _lib.lib.spt_attn_use_mfma(-2)
-    if (mode & 3) == 0:
+    if (_attn_mode(mode) & 3) == 0:
         return None
     n, e = qkv.shape[0], edge_attr.shape[0]
     pad = torch.nn.functional.pad
@@ -897,7 +914,7 @@ def _matrix_pipe_pad(qkv, ecsr, edge_attr, Wk, bk, Wq, bq, Wv, bv, H, D):
     return qp, eap, wk, bkp, wq, bqp, wv, bvp, Dv
 
 
-def _matrix_pipe_split(qkv, edge_attr, Wk, Wq, Wv, H, D):
+def _matrix_pipe_split(qkv, edge_attr, Wk, Wq, Wv, H, D, mode=None):
     """(G, J, Dv) when a head layout other than the built (16, 4, 4) decomposes into G x J passes
     of it (H = 16 G, qk_dim 4, value dim 4 J, in_rpe_dim 32, all three RPE encoders, a matrix-pipe
     precision active); None for the built shape itself and for everything else (generic kernels)."""
@@ -911,10 +928,7 @@ def _matrix_pipe_split(qkv, edge_attr, Wk, Wq, Wv, H, D):
     Dv = C // H
     if Dv % 4 or (H == 16 and Dv == 4):
         return None
-    mode = _precision.attention_mode()
-    if mode < 0:
-        mode = _lib.lib.spt_attn_use_mfma(-2)          # query: any value < -1 leaves the default
-    if (mode & 3) == 0:
+    if (_attn_mode(mode) & 3) == 0:
         return None
     return H // 16, Dv // 4, Dv
 

@@ -24,11 +24,19 @@ switch, configs/trainer/gpu.yaml:7-10).
 
 The mode travels PER CALL: ``matrix_precision(mode)`` (a context manager on a ``contextvars``
 variable: per thread / task) and ``SPT(..., matrix_precision=...)`` make the autograd wrappers of
-``ops`` pass the mode word to the ``*_ex`` entry points of the C ABI, which read no process-wide
-state - two models at different precisions, on different streams or threads, never change each
-other's arithmetic (tests/test_modes_gpu.py).  The backward of an op runs in the mode its forward
-ran in.  ``set_matrix_precision`` is the older process-wide default (the library's own setters):
-it applies wherever no per-call mode is active.
+``ops`` pass the mode word to the ``*_ex`` entry points of the C ABI - two models at different
+precisions, on different streams or threads, never change each other's arithmetic
+(tests/test_modes_gpu.py).  ``set_matrix_precision`` is the older process-wide default (the
+library's own setters): it applies wherever no per-call mode is active.
+
+A field of the attention's mode word that no context sets is OPEN, and the library fills an open
+field from its process-wide switches (``spt_attn_resolve_mode``, the one place that reads them).
+``ops.edge_attention`` does that ONCE, when the forward is called, and hands the explicit word to
+the forward, to the tile records and - saved on the autograd node - to the backward: the backward
+of an attention runs in the mode its forward ran in even when a switch or a context changes in
+between (tests/test_attention_gpu.py::test_backward_runs_in_the_mode_of_its_forward).  The fused
+MLP and the skinny Linears pass -1 where no context is active; their entries read their own
+switches when called.
 """
 import contextlib
 import contextvars
@@ -67,9 +75,10 @@ _order = contextvars.ContextVar("spt_attn_bwd_order", default=None)
 
 
 def attention_mode():
-    """Mode word for ``spt_edge_attn_*_ex_f32``: -1 (library defaults) unless a per-call precision
-    or a per-call edge order of the attention backward is active (bits 0-1 precision, bits 6-7
-    edge order; include/spt_hip.h)."""
+    """What the active contexts say about the attention's mode word: -1 (every field open) unless
+    a per-call precision or a per-call edge order of the attention backward is active (bits 0-1
+    precision, bits 6-7 edge order; include/spt_hip.h).  ``ops.edge_attention`` resolves the open
+    fields once per call (``spt_attn_resolve_mode``)."""
     mode, order = _active.get(), _order.get()
     if mode is None and order is None:
         return -1

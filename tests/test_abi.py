@@ -130,3 +130,131 @@ def test_round4_dispatch_queries_and_argument_checks():
     assert L.spt_fused_linear_fwd_use_x3(0) == prev and L.spt_fused_linear_fwd_use_x3(prev) == 0
     prev = L.spt_attn_bwd_el_full_line(-1)
     assert L.spt_attn_bwd_el_full_line(prev) == prev
+
+
+# the mode word of the attention entries (include/spt_hip.h)
+F32, SPLIT, BF16 = 1, 2, 3
+PER_NODE, PACKED, EDGE_LANE = 1 << 4, 2 << 4, 3 << 4
+TARGET, SOURCE = 1 << 6, 2 << 6
+FORM, ORDER = 3 << 4, 3 << 6
+
+
+def _switches(L):
+    """The three process switches, read through their setters' query forms and put back."""
+    packed = L.spt_attn_bwd_packed(2)
+    L.spt_attn_bwd_packed(packed)
+    return L.spt_attn_use_mfma(-2), packed, L.spt_attn_bwd_el_target_order(-1)
+
+
+def test_attention_mode_word_is_resolved_in_one_place():
+    """spt_attn_resolve_mode: idempotent, an open field follows its process switch, a field the
+    caller wrote does not, and resolving changes no switch."""
+    from superpoint_transformer_amd import _lib
+    L = _lib.lib
+    res = L.spt_attn_resolve_mode
+    before = _switches(L)
+    words = [-1, 0, F32, SPLIT, BF16, PER_NODE, PACKED, EDGE_LANE, TARGET, SOURCE,
+             SPLIT | PACKED | SOURCE, BF16 | EDGE_LANE | TARGET]
+    for m in words:
+        r = res(m)
+        assert r >= 0 and res(r) == r, f"{m:#x}"
+        assert r & FORM and r & ORDER                       # every field explicit
+        if m >= 0:
+            assert r & 3 == m & 3
+            assert not (m & FORM) or r & FORM == m & FORM
+            assert not (m & ORDER) or r & ORDER == m & ORDER
+    assert _switches(L) == before
+    try:
+        for prec in (0, 1, 2, 3):
+            L.spt_attn_use_mfma(prec)
+            assert res(-1) & 3 == prec and res(BF16) & 3 == BF16 and res(0) & 3 == 0
+            assert res(res(-1)) == res(-1)
+        L.spt_attn_use_mfma(before[0])
+        for packed, form in ((0, PER_NODE), (1, PACKED), (2, EDGE_LANE)):
+            L.spt_attn_bwd_packed(packed)
+            assert res(-1) & FORM == form and res(SPLIT) & FORM == form
+            assert res(SPLIT | PACKED) & FORM == PACKED and res(SPLIT | PER_NODE) & FORM == PER_NODE
+        L.spt_attn_bwd_packed(before[1])
+        for on, order in ((0, SOURCE), (1, TARGET)):
+            L.spt_attn_bwd_el_target_order(on)
+            assert res(-1) & ORDER == order and res(SPLIT | EDGE_LANE) & ORDER == order
+            assert res(SPLIT | TARGET) & ORDER == TARGET and res(SPLIT | SOURCE) & ORDER == SOURCE
+            # a word resolved under one setting keeps its fields under the other
+            kept = res(-1)
+            L.spt_attn_bwd_el_target_order(1 - on)
+            assert res(kept) == kept
+    finally:
+        L.spt_attn_use_mfma(before[0])
+        L.spt_attn_bwd_packed(before[1])
+        L.spt_attn_bwd_el_target_order(before[2])
+    assert _switches(L) == before
+
+
+RPE, SRC, IDS, VIEW = 1, 2, 4, 8
+VALU, R_PER_NODE, R_PACKED, R_SOURCE, R_TARGET = range(5)
+REFUSED = "refused"
+BUILT = (16, 4, 4, 32)
+#   word, operands, workspace ("ex" | "tables"), (n, e), shape, expected
+ROUTES = [
+    (-1, RPE | SRC | IDS, "ex", (90, 160), BUILT, R_TARGET),                 # default word, src + tile ids
+    (-1, RPE | SRC | VIEW, "ex", (90, 160), BUILT, R_TARGET),                # default word, src + view
+    (-1, RPE, "ex", (90, 160), BUILT, R_PACKED),                             # default word, nothing
+    (-1, RPE | SRC | IDS | VIEW, "tables", (90, 160), BUILT, R_PACKED),      # everything but the scratch
+    (-1, RPE | VIEW, "ex", (90, 160), BUILT, R_SOURCE),                      # view only (no src)
+    (-1, RPE | IDS | VIEW, "ex", (90, 160), BUILT, R_SOURCE),                # (target-order ids are ignored)
+    (SPLIT | SOURCE, RPE | SRC | IDS | VIEW, "ex", (90, 160), BUILT, R_SOURCE),   # explicit source, view
+    (SPLIT | SOURCE, RPE | SRC | IDS, "ex", (90, 160), BUILT, R_PACKED),     # explicit source, no view
+    (SPLIT | TARGET, RPE | VIEW, "ex", (90, 160), BUILT, REFUSED),           # explicit target, view, no src
+    (SPLIT | TARGET, RPE | SRC, "ex", (90, 160), BUILT, R_PACKED),           # (no edge-lane route possible)
+    (SPLIT | EDGE_LANE, RPE, "ex", (90, 160), BUILT, REFUSED),               # explicit edge lane, nothing
+    (SPLIT | EDGE_LANE, RPE | SRC | IDS | VIEW, "tables", (90, 160), BUILT, REFUSED),
+    (SPLIT | EDGE_LANE, RPE | SRC | IDS, "ex", (90, 160), BUILT, R_TARGET),
+    (F32 | EDGE_LANE, RPE | SRC | IDS | VIEW, "ex", (90, 160), BUILT, REFUSED),   # (needs a bf16-pipe precision)
+    (SPLIT | PER_NODE, RPE | SRC | IDS | VIEW, "ex", (90, 160), BUILT, R_PER_NODE),
+    (SPLIT | PACKED, RPE | SRC | IDS | VIEW, "ex", (90, 160), BUILT, R_PACKED),
+    (SPLIT | PACKED, RPE, "tables", (90, 0), BUILT, R_PER_NODE),             # explicit packed at e == 0
+    (F32, RPE | SRC | IDS | VIEW, "ex", (90, 160), BUILT, R_PER_NODE),       # precision 1
+    (BF16, RPE | SRC | IDS | VIEW, "ex", (90, 160), BUILT, R_TARGET),        # precision 3, default
+    (0, RPE | SRC | IDS | VIEW, "ex", (90, 160), BUILT, VALU),               # precision 0
+    (-1, RPE | SRC | IDS | VIEW, "ex", (90, 160), (16, 4, 8, 32), VALU),     # Dv 8
+    (-1, RPE, "tables", (90, 160), (64, 4, 1, 32), -4),                      # H * D = 256
+    (-1, SRC | IDS | VIEW, "ex", (90, 160), BUILT, VALU),                    # no RPE
+]
+
+
+def _route(L, word, operands, ws, ne, shape):
+    (n, e), (H, D, Dv, F) = ne, shape
+    nb = (L.spt_edge_attn_bwd_ex_workspace_bytes(n, e, H, D, Dv, F) if ws == "ex"
+          else L.spt_edge_attn_bwd_workspace_bytes(H, D, Dv, F))
+    return L.spt_edge_attn_bwd_route(n, e, H, D, Dv, F, operands, word, nb)
+
+
+def test_attention_backward_route_table():
+    """spt_edge_attn_bwd_route against the route table of include/spt_hip.h, as a literal list: the
+    function the backward entry itself switches on, so a silent downgrade is a visible value."""
+    from superpoint_transformer_amd import _lib
+    L = _lib.lib
+    before = _switches(L)
+    assert before == (2, 2, 1), "the cases are written for the default process switches"
+    for i, (word, operands, ws, ne, shape, want) in enumerate(ROUTES):
+        got = _route(L, word, operands, ws, ne, shape)
+        if want == REFUSED:
+            assert got == -1 and "backward" in _lib.last_error(), f"case {i}: {got}"
+        else:
+            assert got == want, f"case {i}: route {got}, expected {want}"
+        # a resolved word routes like the word it came from: defaults stay preferences
+        assert _route(L, L.spt_attn_resolve_mode(word), operands, ws, ne, shape) == got, f"case {i}"
+    assert "unsupported attention shape" in _lib.last_error()            # (the last failing case: -4)
+    everything = (RPE | SRC | IDS | VIEW, "ex", (90, 160), BUILT)
+    try:
+        L.spt_attn_bwd_packed(1)
+        assert _route(L, -1, *everything) == R_PACKED
+        L.spt_attn_bwd_packed(0)
+        assert _route(L, -1, *everything) == R_PER_NODE
+        L.spt_attn_bwd_packed(before[1])
+        L.spt_attn_bwd_el_target_order(0)
+        assert _route(L, -1, *everything) == R_SOURCE
+    finally:
+        L.spt_attn_bwd_packed(before[1])
+        L.spt_attn_bwd_el_target_order(before[2])
+    assert _switches(L) == before

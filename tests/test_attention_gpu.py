@@ -242,13 +242,20 @@ def _degree_graph(gen, degrees):
 ])
 @pytest.mark.parametrize("packed,target_order", [(2, 1), (2, 0), (1, None), (0, None)],
                          ids=["edge-lane-target-order", "edge-lane-source-order", "packed", "per-node"])
-def test_attention_backward_tilings_match_oracle(degrees, packed, target_order, dev):
+def test_attention_backward_tilings_match_oracle(degrees, packed, target_order, dev, monkeypatch):
     """The edge-lane backward over the edge stream in target order (the default) and in source
     order, the packed backward (16-edge tiles over the edge stream, two node contexts per pass,
     extra passes when a tile holds more nodes) and the per-node tiling, against the f64 oracle
     on graphs built to hit the tile / node boundary cases (short last tiles included: the
-    edge counts are 160, 144, 192, 361 and 9)."""
-    from superpoint_transformer_amd import _lib, nn as N
+    edge counts are 160, 144, 192, 361 and 9).  The route the backward's plan reports is the one
+    the case names: a silent downgrade to another kernel fails here."""
+    from superpoint_transformer_amd import _lib, nn as N, ops
+    routes, real_plan = [], ops._attn_bwd_plan
+
+    def plan(*a, **k):
+        routes.append(real_plan(*a, **k))
+        return routes[-1]
+    monkeypatch.setattr(ops, "_attn_bwd_plan", plan)
     gen = torch.Generator().manual_seed(sum(degrees) + len(degrees))
     n, H, D, dim, F = len(degrees), 16, 4, 64, 32
     ei = _degree_graph(gen, degrees)
@@ -269,6 +276,9 @@ def test_attention_backward_tilings_match_oracle(degrees, packed, target_order, 
         _lib.lib.spt_attn_bwd_packed(prev)
         if prev_to is not None:
             _lib.lib.spt_attn_bwd_el_target_order(prev_to)
+    want = {(2, 1): ops.ATTN_ROUTE_EDGE_LANE_TARGET, (2, 0): ops.ATTN_ROUTE_EDGE_LANE_SOURCE,
+            (1, None): ops.ATTN_ROUTE_PACKED, (0, None): ops.ATTN_ROUTE_PER_NODE}[packed, target_order]
+    assert [r[0] for r in routes] == [want]
     p = {k: v.detach().cpu().double().requires_grad_() for k, v in blk.named_parameters()}
     x64, ea64 = x.double().requires_grad_(), ea.double().requires_grad_()
     deg = torch.tensor(degrees).double().clamp(min=1)
@@ -284,6 +294,43 @@ def test_attention_backward_tilings_match_oracle(degrees, packed, target_order, 
     _check(ead.grad, ea64.grad, "g_edge_attr")
     for k, v in blk.named_parameters():
         _check(v.grad, p[k].grad, "g_" + k, rel_to_max=True)
+
+
+def test_backward_runs_in_the_mode_of_its_forward(dev):
+    """The mode word is resolved when the forward is called and saved on the autograd node: a
+    process switch flipped between forward and backward does not reach the backward.  Forward
+    in source order, switch to target order, backward - every gradient is bit for bit the one
+    of a run that stayed in source order (that order has no atomics: run-to-run identical bits,
+    tests/test_reproducible_gpu.py; the target order's float atomics would show)."""
+    from superpoint_transformer_amd import _lib, nn as N
+    degrees = [1] * 40 + [2] * 30 + [3] * 20
+    gen = torch.Generator().manual_seed(sum(degrees) + len(degrees))
+    n, H, D, dim, F = len(degrees), 16, 4, 64, 32
+    ei = _degree_graph(gen, degrees).to(dev)
+    blk = N.SelfAttentionBlock(dim, num_heads=H, out_dim=None, qk_dim=D, in_rpe_dim=F,
+                               k_rpe=True, q_rpe=True, v_rpe=True).to(dev)
+    x = torch.randn(n, dim, generator=gen).to(dev)
+    ea = (torch.randn(ei.shape[1], F, generator=gen) * 0.5).to(dev)
+    gw = torch.randn(n, dim, generator=gen).to(dev)
+
+    def run(order_at_backward):
+        blk.zero_grad(set_to_none=True)
+        xd, ead = x.clone().requires_grad_(), ea.clone().requires_grad_()
+        _lib.lib.spt_attn_bwd_el_target_order(0)
+        out = blk(xd, ei, edge_attr=ead)
+        _lib.lib.spt_attn_bwd_el_target_order(order_at_backward)
+        (out * gw).sum().backward()
+        return [xd.grad, ead.grad] + [p.grad.clone() for p in blk.parameters()]
+
+    prev = _lib.lib.spt_attn_bwd_el_target_order(-1)
+    try:
+        ref = run(0)
+        got = run(1)
+    finally:
+        _lib.lib.spt_attn_bwd_el_target_order(prev)
+    assert len(got) == len(ref) and all(g is not None for g in ref)
+    for i, (a, b) in enumerate(zip(got, ref)):
+        assert torch.equal(a, b), f"gradient {i} differs"
 
 
 @pytest.mark.parametrize("mode", [2, 1, 0])
