@@ -1453,6 +1453,60 @@ int spt_augment_color_f32(const float* color, float* out, int64_t n, int64_t ld_
                           double lo, double hi, const float* range6, float blend,
                           float one_minus_blend, spt_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * GridSampling3D: voxel keys, one sort, one-pass groups        (csrc/voxel.hip)
+ * GridSampling3D._process / _group_data (src/transforms/sampling.py:86-468).
+ *
+ * pos: f32, coordinate a of point i at pos[i * ld + a] (a block of a wider table works);
+ * batch: int64 [n] or NULL; 1 <= n < 2^31.  The integer coordinate of a point is
+ * rintf(pos / size): a correctly rounded IEEE f32 division, then round half to even - bit for
+ * bit torch.round(pos / size).  Voxels are numbered in lexicographic order of
+ * (batch, z, y, x), which is the order consecutive_cluster leaves of grid_cluster / voxel_grid.
+ *
+ * spt_voxel_bounds_f32: record = 10 device int32: min and max of x, y, z, min and max of
+ *   batch (0, 0 without one), the number of points with a non-finite coordinate, the number of
+ *   points with a coordinate or a batch index outside [-(2^31 - 1), 2^31 - 1].  Neither kind takes
+ *   part in the bounds.  One set of integer atomics per workgroup; bitwise reproducible.
+ * spt_voxel_groups_f32: the HOST hands back the minima (origin: x, y, z, batch) and the field
+ *   widths (bits: x, y, z, batch; their sum in [1, 63]) it derived from the record.  Packs
+ *   (batch, z, y, x) - origin into a u64 key, sorts (key, point) by a stable LSD radix sort over
+ *   the significant bits only (low word, then high word when the key is wider than 32 bits),
+ *   marks run heads, scans them and writes
+ *     pointers [V + 1] int64 (capacity n + 1), cluster [n] int64 (voxel of every point),
+ *     order [n] int64 (points sorted by voxel, ascending inside a voxel), last [V] int64
+ *     (capacity n: highest point index of the voxel), coords [V, 3] int32 (capacity n; x, y, z,
+ *     NOT shifted), *count = V (device int64).
+ *   No kernel uses a key as an address.  ws: spt_voxel_groups_workspace_bytes(n, total bits).
+ * spt_voxel_mean_f32: out[v * ld_out + c] = (sum of x[p * ld_x + c] over the voxel's points in
+ *   ascending point order, from 0.0f) / (float)count - torch's CPU index_add arithmetic.  Runs
+ *   longer than 512 points are summed by a whole wave: lane l adds elements l, l + 64, ... in
+ *   order, then a fixed butterfly; no float atomics, bitwise reproducible either way.
+ *   normalize != 0 (cols == 3): the row is then divided by sqrtf(x^2 + y^2 + z^2); a zero mean
+ *   gives NaN, as the reference does.
+ * spt_voxel_hist_i64: labels int64 [n], 1 <= n_bins <= 256.  hist (nullable) [V, n_bins] int64
+ *   label counts; vote (nullable) [V] int64 = argmax of the counts, ties to the lowest label,
+ *   without writing them.  A label outside [0, n_bins) sets *status (device int32) to 1 and is
+ *   not counted.  Each row is owned by one lane or one wave: no global atomics.
+ * spt_voxel_last: out [V] int64 = the point of the voxel with the greatest
+ *   (rand32(seed, point), point); use_seed == 0: the highest point index.
+ * ---------------------------------------------------------------------- */
+int spt_voxel_bounds_f32(const float* pos, int64_t n, int64_t ld, float size,
+                         const int64_t* batch, int32_t* record, spt_stream_t stream);
+size_t spt_voxel_groups_workspace_bytes(int64_t n, int key_bits);
+int spt_voxel_groups_f32(const float* pos, int64_t n, int64_t ld, float size,
+                         const int64_t* batch, const int64_t* origin, const int* bits,
+                         int64_t* pointers, int64_t* cluster, int64_t* order, int64_t* last,
+                         int32_t* coords, int64_t* count, void* ws, size_t ws_bytes,
+                         spt_stream_t stream);
+int spt_voxel_mean_f32(const float* x, int64_t n, int cols, int64_t ld_x,
+                       const int64_t* pointers, const int64_t* order, int64_t num_voxels,
+                       int normalize, float* out, int64_t ld_out, spt_stream_t stream);
+int spt_voxel_hist_i64(const int64_t* labels, int64_t n, const int64_t* pointers,
+                       const int64_t* order, int64_t num_voxels, int n_bins, int64_t* hist,
+                       int64_t* vote, int32_t* status, spt_stream_t stream);
+int spt_voxel_last(const int64_t* pointers, const int64_t* order, int64_t n, int64_t num_voxels,
+                   uint64_t seed, int use_seed, int64_t* out, spt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

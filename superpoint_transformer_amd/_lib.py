@@ -260,6 +260,13 @@ SIGNATURES = {
                                            _p, _p]),
     "spt_augment_color_f32": (_int, [_p, _p, _i64, _i64, _i64, _int, _c.c_uint64, _f64, _f64, _f64,
                                      _f64, _p, _f32, _f32, _p]),
+    "spt_voxel_bounds_f32": (_int, [_p, _i64, _i64, _f32, _p, _p, _p]),
+    "spt_voxel_groups_workspace_bytes": (_sz, [_i64, _int]),
+    "spt_voxel_groups_f32": (_int, [_p, _i64, _i64, _f32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz,
+                                    _p]),
+    "spt_voxel_mean_f32": (_int, [_p, _i64, _int, _i64, _p, _p, _i64, _int, _p, _i64, _p]),
+    "spt_voxel_hist_i64": (_int, [_p, _i64, _p, _p, _i64, _int, _p, _p, _p, _p]),
+    "spt_voxel_last": (_int, [_p, _p, _i64, _i64, _c.c_uint64, _int, _p, _p]),
 }
 
 

@@ -14,7 +14,7 @@ __all__ = ["horizontal_edge_features", "EDGE_FEATURE_COLUMNS", "NodeSize", "Samp
            "PointFeatures", "AddKeysTo", "NAGJitterKey", "RandomTiltAndRotate",
            "RandomAnisotropicScale", "RandomAxisFlip", "NAGDropoutColumns", "NAGDropoutRows",
            "NAGColorAutoContrast", "NAGColorDrop", "GeometricAugmentation", "FeatureAugmentation",
-           "ColorAugmentation"]
+           "ColorAugmentation", "GridSampling3D", "SaveNodeIndex", "DataTo"]
 
 EDGE_FEATURE_COLUMNS = [
     "mean_off_x", "mean_off_y", "mean_off_z", "std_off_x", "std_off_y", "std_off_z",
@@ -83,6 +83,195 @@ def vertical_edge_features(child, parent):
             _lib.ptr(out), _lib.stream_ptr(dev))
     _lib.check(st, "spt_vertical_edge_features_f32")
     return out
+
+
+class DataTo:
+    """``DataTo(device)`` (src/transforms/device.py:9-20), the first ``pre_transform`` of
+    configs/datamodule/semantic/default.yaml: the ``Data`` itself when it already lives on
+    ``device``, else a new ``Data`` whose tensors, ``Cluster`` and ``InstanceData`` were moved."""
+
+    def __init__(self, device):
+        self.device = device if isinstance(device, torch.device) else torch.device(device)
+
+    def __call__(self, data):
+        from .data import Data
+        if data.device == self.device:
+            return data
+        out = Data()
+        for key, item in data:
+            out[key] = item.to(self.device) if hasattr(item, "to") else item
+        out.num_nodes = data._num_nodes
+        return out
+
+
+class SaveNodeIndex:
+    """``SaveNodeIndex(key)`` (src/transforms/sampling.py:56-69): ``data[key] = arange(N)`` on
+    the data's device, to track nodes from the output back to the input; the default chain
+    stores it as ``'sub'``, which ``GridSampling3D`` turns into the raw-point ``Cluster``."""
+
+    DEFAULT_KEY = "node_id"
+
+    def __init__(self, key=None):
+        self.key = key if key is not None else self.DEFAULT_KEY
+
+    def __call__(self, data):
+        data[self.key] = torch.arange(0, data.pos.shape[0], device=data.device)
+        return data
+
+
+def _instance_data_dense_torch(cluster, obj, count, y):
+    """``InstanceData(cluster, obj, count, y, dense=True)`` (src/data/instance.py:70-98) as a
+    torch composition, for CPU tensors: duplicate (cluster, obj) pairs merged, counts summed,
+    ``y`` of the last holder of each pair."""
+    from .instance import InstanceData
+    cluster, obj, count, y = (t.long() for t in (cluster, obj, count, y))
+    key = cluster * (obj.max() + 1) + obj
+    uniq, inv = torch.unique(key, sorted=True, return_inverse=True)
+    # the LAST holder (an index_put_ with duplicates keeps it only on one thread: amax says it)
+    perm = torch.zeros(uniq.numel(), dtype=torch.int64, device=key.device)
+    perm.scatter_reduce_(0, inv, torch.arange(inv.numel(), device=key.device), "amax")
+    merged = torch.zeros(uniq.numel(), dtype=torch.int64, device=key.device).index_add_(0, inv, count)
+    index = cluster[perm]
+    sizes = torch.bincount(index, minlength=int(index.max()) + 1)
+    if not bool((sizes > 0).all()):
+        raise AssertionError("Indices must be dense")
+    pointers = torch.cat([sizes.new_zeros(1), sizes.cumsum(0)])
+    return InstanceData(pointers, obj[perm], merged, y[perm])
+
+
+class GridSampling3D:
+    """``GridSampling3D`` (src/transforms/sampling.py:86-468), the voxelisation that opens the
+    preprocessing chain, with the reference's signature: ``voxel.voxel_groups`` on
+    ``data.pos`` (and ``data.batch`` when present), then every key of ``data`` in stored order
+    exactly as ``_group_data`` walks them:
+
+      * ``obj`` / ``obj_pred``: ``InstanceData(cluster, item, ones, y or zeros, dense=True)``, or
+        ``item.merge(cluster)`` for an ``InstanceData`` (``y`` is read from the data AS STORED
+        at that moment, like the reference: keep ``obj`` in front of ``y``);
+      * ``sub``: the ``Cluster`` of the item's values per voxel, built from the groups'
+        ``pointers`` and ``order`` without a second sort; it must be a 1-D integer tensor;
+      * any other ``Cluster`` / ``InstanceData`` and any key whose name holds ``edge``:
+        ``NotImplementedError``;
+      * non-tensors and tensors with another first dimension than ``num_nodes``: untouched;
+      * ``mode='last'``, and ``batch`` / ``node_id`` in any mode: ``item[representative]``;
+      * a key of ``hist_key``: ``[V, n_bins]`` int64 histogram; ``y`` / ``super_index`` /
+        ``is_val`` otherwise: the majority label, ties to the lowest (bool goes through int and
+        comes back as bool);
+      * everything else: the mean (``voxel.group_mean``; integer tensors floor); ``normal`` is
+        divided by its norm afterwards.
+
+    The representative of a voxel is its highest point index in ``mode='mean'``.  In
+    ``mode='last'`` the reference shuffles the cloud first; here the representative is drawn
+    per voxel by ``voxel.group_last`` under a seed taken from torch's CPU generator
+    (``torch.manual_seed`` makes it reproducible), uniform over the voxel's points like the
+    shuffle; ``shuffle = False`` on the instance keeps the highest index instead.  The points of
+    ``sub`` inside a voxel stay in ascending order (the reference's follow its shuffle; nothing
+    reads that order).  ``quantize_coords`` stores the integer voxel coordinates as ``coords``
+    [V, 3] int32, minus their column minimum unless ``allow_negative_coords``;
+    ``grid_size = tensor([size])``.  ``chunk_size`` is accepted and ignored: it only bounds the
+    reference's temporaries.  ``groups_`` keeps the last call's ``VoxelGroups``."""
+
+    _VOTING_KEYS = ("y", "super_index", "is_val")
+    _INSTANCE_KEYS = ("obj", "obj_pred")
+    _CLUSTER_KEYS = ("sub",)
+    _LAST_KEYS = ("batch", SaveNodeIndex.DEFAULT_KEY)
+    _NORMAL_KEYS = ("normal",)
+
+    def __init__(self, size, quantize_coords=False, allow_negative_coords=False, mode="mean",
+                 hist_key=None, hist_size=None, inplace=False, chunk_size=10_000_000,
+                 verbose=False):
+        hist_key = [] if hist_key is None else hist_key
+        hist_size = [] if hist_size is None else hist_size
+        hist_key = [hist_key] if isinstance(hist_key, str) else hist_key
+        hist_size = [hist_size] if isinstance(hist_size, int) else hist_size
+        assert isinstance(hist_key, list)
+        assert isinstance(hist_size, list)
+        assert len(hist_key) == len(hist_size)
+        assert mode in ("mean", "last")
+        self.grid_size = size
+        self.quantize_coords = quantize_coords
+        self.allow_negative_coords = allow_negative_coords
+        self.mode = mode
+        self.bins = {k: v for k, v in zip(hist_key, hist_size)}
+        self.inplace = inplace
+        self.chunk_size = chunk_size
+        self.shuffle = True
+        self.groups_ = None
+
+    def _instance(self, data, item, cluster):
+        from .instance import InstanceData
+        if isinstance(item, InstanceData):
+            if item.device.type == "cuda":
+                return item.merge(cluster)
+            return _instance_data_dense_torch(cluster[item.indices], item.obj, item.count, item.y)
+        y = data.y if data.get("y") is not None else torch.zeros_like(item)
+        if y.shape != item.shape:
+            raise ValueError(
+                f"instance labels need one semantic label per point, but data.y is "
+                f"{tuple(y.shape)}: store the instance key in front of 'y'")
+        count = torch.ones_like(item)
+        if item.is_cuda:
+            return InstanceData(cluster, item, count, y, dense=True)
+        return _instance_data_dense_torch(cluster, item, count, y)
+
+    def __call__(self, data_in):
+        import re
+        from . import voxel
+        from .data import Cluster
+        from .instance import InstanceData
+        from .segment import _draw_seed
+        data = data_in if self.inplace else data_in.clone()
+        groups = voxel.voxel_groups(data.pos, self.grid_size, data.get("batch"))
+        self.groups_ = groups
+        pick = groups.last
+        if self.mode == "last" and self.shuffle:
+            pick = voxel.group_last(groups, _draw_seed())
+        num_nodes = data.num_nodes
+        for key, item in data:
+            if re.search("edge", key):
+                raise NotImplementedError("Edges not supported. Wrong data type.")
+            if key in self._INSTANCE_KEYS:
+                data[key] = self._instance(data, item, groups.cluster)
+                continue
+            if key in self._CLUSTER_KEYS:
+                if not (torch.is_tensor(item) and item.dim() == 1 and not item.is_floating_point()):
+                    raise NotImplementedError(
+                        f"Cannot merge '{key}' with data type: {type(item)} into a Cluster object. "
+                        "Only supports 1D Tensor of integers.")
+                data[key] = Cluster(groups.pointers, item[groups.order])
+                continue
+            if isinstance(item, (Cluster, InstanceData)):
+                raise NotImplementedError(f"Cannot merge '{key}' with data type: {type(item)}")
+            if not torch.is_tensor(item) or item.dim() == 0 or item.size(0) != num_nodes:
+                continue
+            if self.mode == "last" or key in self._LAST_KEYS:
+                data[key] = item[pick]
+                continue
+            is_bool = item.dtype == torch.bool
+            if is_bool:
+                item = item.int()
+            normalize = key in self._NORMAL_KEYS
+            if key in self._VOTING_KEYS or key in self.bins:
+                if item.dim() != 1:
+                    raise NotImplementedError(
+                        f"'{key}': only 1-D labels are voted or binned (the reference sums 2-D "
+                        "items as ready-made histograms; not built)")
+                if key in self.bins:
+                    out = voxel.group_histogram(item, groups, self.bins[key])
+                else:
+                    out = voxel.group_vote(item, groups)
+                if normalize:
+                    out = out / out.norm(dim=1).view(-1, 1)
+            else:
+                out = voxel.group_mean(item, groups, normalize=normalize)
+            data[key] = out.bool() if is_bool else out
+        if self.quantize_coords:
+            coords = groups.coords.clone()
+            if not self.allow_negative_coords:
+                coords -= torch.min(coords, dim=0, keepdim=True).values
+            data.coords = coords
+        data.grid_size = torch.tensor([self.grid_size])
+        return data
 
 
 class PartitionAdjacency:
