@@ -12,6 +12,13 @@ caller computes their length, the outputs - cut to the byte out of a guarded are
      each test below); integer outputs bit-exact;
   3. the result is bit-identical to the same call through the normal grow-only ``_workspace``.
 
+Every call then runs a third time on an arena whose guards AND contents are 0xFF (NaN in every
+float format, -1 as an integer), through the wrappers with ``torch.empty`` and its kin handing
+out NaN as well: a workgroup that skips its partial table, a scan that leaves a partial
+unwritten or an output element no kernel wrote is then read as NaN instead of as what the last
+call of the same shape left there.  Two more assertions: these guards are intact too, and the
+result is bit-identical to the generous run.
+
 Scan lengths stay below 2^21: even a partials region with no room at all would then overflow by
 2 KiB at most, far inside a guard.
 
@@ -67,7 +74,7 @@ import numpy as np
 import pytest
 import torch
 
-from guarded import GuardedArena, exact_workspaces
+from guarded import GuardedArena, exact_workspaces, poisoned_fresh_tensors
 from oracle import spt_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -136,21 +143,36 @@ class Exact:
         return self.arena.take(nbytes, dtype, shape, label=label)
 
 
+class Poisoned(Exact):
+    """Exact, with NaN in every byte the call may read without having written it: the guards and
+    the contents of the workspace and of the outputs are 0xFF (NaN as a float, -1 as an integer)."""
+
+    def __init__(self, dev):
+        self.dev = dev
+        self.arena = GuardedArena(dev, guard_byte=0xFF, fill_byte=0xFF)
+
+
 def c_call(dev, call, what):
-    """``call(alloc)`` through the C ABI with the generous and with the exact allocator: guards
-    intact, same bits; returns the exact run's result."""
+    """``call(alloc)`` through the C ABI with the generous, the exact and the poisoned allocator:
+    guards intact, same bits; returns the exact run's result."""
     with torch.cuda.device(dev):
         gen = call(Generous(dev))
         ex_alloc = Exact(dev)
         ex = call(ex_alloc)
+        po_alloc = Poisoned(dev)
+        po = call(po_alloc)
     ex_alloc.arena.check()
     same_bits(gen, ex, what)
+    po_alloc.arena.check()
+    same_bits(gen, po, what + " (poisoned scratch and outputs)")
     return ex
 
 
 def wrapped(dev, fn, what, sizes=(), any_of=(), bits_of=None):
-    """``fn()`` through the Python wrappers with the normal ``_workspace`` and with the arena in
-    its place; ``sizes``: byte counts that must have been asked of the arena (the entry point ran,
+    """``fn()`` through the Python wrappers with the normal ``_workspace``, with the arena in its
+    place, and with a NaN-filled arena while every fresh floating tensor is NaN-filled too (a
+    partial table, an output or an intermediate read without having been written in the same
+    call then changes the result); ``sizes``: byte counts that must have been asked of the arena (the entry point ran,
     with exactly what its size function returned); ``any_of``: at least one of these was;
     ``bits_of``: the part of the result compared bit for bit (default: all of it)."""
     gen = fn()
@@ -164,6 +186,12 @@ def wrapped(dev, fn, what, sizes=(), any_of=(), bits_of=None):
     assert not any_of or any(int(nb) in asked for nb in any_of), (what, any_of, sorted(set(asked)))
     pick = bits_of or (lambda r: r)
     same_bits(pick(gen), pick(ex), what)
+    poisoned = GuardedArena(dev, guard_byte=0xFF, fill_byte=0xFF)
+    with poisoned_fresh_tensors(dev):
+        with exact_workspaces(poisoned):              # checks its guards on the way out
+            po = fn()
+    assert poisoned.sizes() == asked, f"{what}: the poisoned run asked for other workspaces"
+    same_bits(pick(gen), pick(po), what + " (poisoned scratch and fresh tensors)")
     return ex
 
 
@@ -353,18 +381,18 @@ def test_csr_build(n, num_seg, dev):
     rperm, rrow = O.csr_view(idx, num_seg)
     d = idx.to(dev)
     lb = lib().lib
-    A = Exact(dev)
     nbytes = lb.spt_csr_build_workspace_bytes(n, num_seg)
-    ws, wsb = A.ws(nbytes)
-    perm = A.out(torch.int32, n, label="perm")
-    rowptr = A.out(torch.int32, num_seg + 1, label="rowptr")
-    with torch.cuda.device(dev):
-        ok(lb.spt_csr_build(P(d), n, num_seg, P(perm), P(rowptr), P(ws), wsb, stream(dev)), "spt_csr_build")
-    A.arena.check()
-    assert torch.equal(perm.cpu(), rperm)
-    assert torch.equal(rowptr, rrow.to(dev))
     gen = build_csr(d, num_seg)
-    same_bits((gen.perm, gen.rowptr), (perm, rowptr), f"csr_build n={n} num_seg={num_seg}")
+    for A in (Exact(dev), Poisoned(dev)):
+        ws, wsb = A.ws(nbytes)
+        perm = A.out(torch.int32, n, label="perm")
+        rowptr = A.out(torch.int32, num_seg + 1, label="rowptr")
+        with torch.cuda.device(dev):
+            ok(lb.spt_csr_build(P(d), n, num_seg, P(perm), P(rowptr), P(ws), wsb, stream(dev)), "spt_csr_build")
+        A.arena.check()
+        assert torch.equal(perm.cpu(), rperm)
+        assert torch.equal(rowptr, rrow.to(dev))
+        same_bits((gen.perm, gen.rowptr), (perm, rowptr), f"csr_build n={n} num_seg={num_seg} {type(A).__name__}")
 
 
 # ---- cluster graph: S * k_max just under and just over 262 143 ---------------------------------------
