@@ -1507,6 +1507,66 @@ int spt_voxel_hist_i64(const int64_t* labels, int64_t n, const int64_t* pointers
 int spt_voxel_last(const int64_t* pointers, const int64_t* order, int64_t n, int64_t num_voxels,
                    uint64_t seed, int use_seed, int64_t* out, spt_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Predictions back to the cloud                                (csrc/predict.hip)
+ * SemanticSegmentationOutput (src/utils/output_semantic.py) and the multi-run inference of
+ * src/models/semantic.py:485-616.
+ *
+ * Every index and position is 64-bit; a size of 0 returns 0 without a launch; no entry reads
+ * device memory from the host or resets a status record: status words are ADDED to, the caller
+ * zeroes the record and reads it when it wants to know.  Nothing read from device memory is used
+ * as an address before it is compared with its bound.
+ *
+ * spt_row_argmax_f32: logits f32 [rows, C], C >= 1.  pred (nullable) int64 [rows] =
+ *   torch.argmax(logits, dim=1) bit for bit: the first maximum, a NaN above every number, the
+ *   first NaN.  hist (nullable, with is_void) int64 [rows, ncols], void counts in the last
+ *   column: is_void[r] (one byte, 0 / 1) = (float)hist[r, ncols - 1] / (float)sum(hist[r, :])
+ *   > 0.5f, a correctly rounded f32 division of the two converted integers (0 / 0 = NaN: 0) -
+ *   SemanticSegmentationOutput.void_mask.
+ * spt_rows_accumulate_f32: acc f32 [N, C], src f32 [n, C], node_id int64 [n]:
+ *   acc[node_id[i], :] = acc[node_id[i], :] + src[i, :], one f32 add per element (a[idx] += b
+ *   for unique ids).  stamp int32 [N] (0 before the first run) takes run >= 1 by one atomic
+ *   exchange per row; stamp != 0 is the reference's `seen`.  An id met twice in one run (the
+ *   exchange returns run) is added once, by whichever occurrence came first, and counted in
+ *   status[0]; an id outside [0, N) writes nothing and is counted in status[1].
+ *   status: int32 [2].
+ * spt_labels_by_index_i64: label int64 [num_label], idx_a int64 [n_a], idx_b (nullable) int64
+ *   [n_b].  out_a (nullable) [n_a]: out_a[i] = label[idx_a[i]]; out_b (nullable) [n_b]:
+ *   out_b[p] = label[idx_a[idx_b[p]]], in the same launch.  target (nullable, with confmat)
+ *   int64 labels of the finest level present ([n_b] with idx_b, else [n_a]); confmat int64
+ *   [C, C], 1 <= C <= 32: confmat[target, label] += 1 for both in [0, C) (anything else is
+ *   void), ADDED to what the buffer holds by 64-bit integer atomics from a per-workgroup LDS
+ *   table, non-zero cells only.  With confmat and both outputs NULL nothing of size n_b is
+ *   written.  An index out of range gives -1, stays out of confmat and is counted:
+ *   status[0] entries of idx_a outside [0, num_label), status[1] entries of idx_b outside
+ *   [0, n_a).  status: int32 [4] (as below).
+ * spt_labels_by_cluster_i64: the same from a Cluster (pointers int64 [num_clusters + 1], points
+ *   int64 [num_points]) without its super_index: every position j in
+ *   [pointers[v], pointers[v + 1]) gets out[points[j]] = label[idx_a ? idx_a[v] : v]; target /
+ *   confmat as above with target indexed by points[j]; out (nullable) [num_points].  The work
+ *   is cut by positions, 1 024 per workgroup pass, each pass finding its clusters by two
+ *   searches of pointers: a cluster of thousands of points costs what thousands of singletons
+ *   cost.  Empty clusters are legal.  status[0] entries of idx_a (or cluster numbers, without
+ *   it) outside [0, num_label): -1 is written; status[1] entries of points outside
+ *   [0, num_points): never written through; status[2] faults of pointers (a decreasing pair,
+ *   pointers[0] != 0, pointers[num_clusters] != num_points): a position that no cluster
+ *   claims is not written.  pointers are only compared, never used as an address.
+ * ---------------------------------------------------------------------- */
+int spt_row_argmax_f32(const float* logits, int64_t rows, int C, const int64_t* hist, int ncols,
+                       int64_t* pred, uint8_t* is_void, spt_stream_t stream);
+int spt_rows_accumulate_f32(float* acc, int64_t N, const float* src, const int64_t* node_id,
+                            int64_t n, int C, int32_t* stamp, int run, int32_t* status,
+                            spt_stream_t stream);
+int spt_labels_by_index_i64(const int64_t* label, int64_t num_label, const int64_t* idx_a,
+                            int64_t n_a, const int64_t* idx_b, int64_t n_b, int64_t* out_a,
+                            int64_t* out_b, const int64_t* target, int C, int64_t* confmat,
+                            int32_t* status, spt_stream_t stream);
+int spt_labels_by_cluster_i64(const int64_t* label, int64_t num_label, const int64_t* idx_a,
+                              const int64_t* pointers, const int64_t* points,
+                              int64_t num_clusters, int64_t num_points, int64_t* out,
+                              const int64_t* target, int C, int64_t* confmat, int32_t* status,
+                              spt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -267,6 +267,10 @@ SIGNATURES = {
     "spt_voxel_mean_f32": (_int, [_p, _i64, _int, _i64, _p, _p, _i64, _int, _p, _i64, _p]),
     "spt_voxel_hist_i64": (_int, [_p, _i64, _p, _p, _i64, _int, _p, _p, _p, _p]),
     "spt_voxel_last": (_int, [_p, _p, _i64, _i64, _c.c_uint64, _int, _p, _p]),
+    "spt_row_argmax_f32": (_int, [_p, _i64, _int, _p, _int, _p, _p, _p]),
+    "spt_rows_accumulate_f32": (_int, [_p, _i64, _p, _p, _i64, _int, _p, _int, _p, _p]),
+    "spt_labels_by_index_i64": (_int, [_p, _i64, _p, _i64, _p, _i64, _p, _p, _p, _int, _p, _p, _p]),
+    "spt_labels_by_cluster_i64": (_int, [_p, _i64, _p, _p, _p, _i64, _i64, _p, _p, _int, _p, _p, _p]),
 }
 
 

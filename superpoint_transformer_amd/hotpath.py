@@ -542,6 +542,14 @@ class SPTInferStep(SPTTrainStep):
         self.last_loss = logits[0]
         return logits
 
+    def output(self):
+        """The last step's level-1 logits as a ``SemanticSegmentationOutput``: predictions per
+        superpoint, voxel and raw point (``output.py``)."""
+        if self.last_loss is None:
+            raise RuntimeError("output() needs a step() first")
+        from .output import SemanticSegmentationOutput
+        return SemanticSegmentationOutput(self.last_loss)
+
 
 class SPTPanopticStep(SPTTrainStep):
     """Config #5 (SuperCluster panoptic training): backbone + semantic heads + edge-affinity

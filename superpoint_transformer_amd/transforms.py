@@ -14,7 +14,7 @@ __all__ = ["horizontal_edge_features", "EDGE_FEATURE_COLUMNS", "NodeSize", "Samp
            "PointFeatures", "AddKeysTo", "NAGJitterKey", "RandomTiltAndRotate",
            "RandomAnisotropicScale", "RandomAxisFlip", "NAGDropoutColumns", "NAGDropoutRows",
            "NAGColorAutoContrast", "NAGColorDrop", "GeometricAugmentation", "FeatureAugmentation",
-           "ColorAugmentation", "GridSampling3D", "SaveNodeIndex", "DataTo"]
+           "ColorAugmentation", "GridSampling3D", "SaveNodeIndex", "NAGSaveNodeIndex", "DataTo"]
 
 EDGE_FEATURE_COLUMNS = [
     "mean_off_x", "mean_off_y", "mean_off_z", "std_off_x", "std_off_y", "std_off_z",
@@ -117,6 +117,18 @@ class SaveNodeIndex:
     def __call__(self, data):
         data[self.key] = torch.arange(0, data.pos.shape[0], device=data.device)
         return data
+
+
+class NAGSaveNodeIndex(SaveNodeIndex):
+    """``NAGSaveNodeIndex(key)`` (src/transforms/sampling.py:72-83): ``SaveNodeIndex`` on every
+    level of a NAG, in place.  The multi-run inference puts it in front of the augmentations, so
+    that the logits of a sampled or shuffled NAG find their rows of the input NAG again."""
+
+    def __call__(self, nag):
+        transform = SaveNodeIndex(key=self.key)
+        for i_level in range(nag.num_levels):
+            nag._list[i_level] = transform(nag._list[i_level])
+        return nag
 
 
 def _instance_data_dense_torch(cluster, obj, count, y):
