@@ -1567,6 +1567,86 @@ int spt_labels_by_cluster_i64(const int64_t* label, int64_t num_label, const int
                               const int64_t* target, int C, int64_t* confmat, int32_t* status,
                               spt_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Panoptic evaluation                                          (csrc/panoptic.hip)
+ * InstanceData.merge / iou_and_size / search_void / remove_void (src/data/instance.py), the
+ * counters of PanopticQuality3D.compute (src/metrics/panoptic.py:225-323) and
+ * scatter_mean_weighted (src/utils/scatter.py:17-38).
+ *
+ * An InstanceData is pointers int64 [G + 1] over P pairs (obj, count, y: int64 [P]).  P, G and
+ * n are in 1 .. 2^31 - 2.  Grouping is one stable radix sort of a key as wide as its extents
+ * need, run heads through the device scan and integer run sums: integer results are exact, no
+ * float and no atomic whose order matters takes part.  No entry reads device memory from the
+ * host; record / status words are ADDED to: the caller zeroes them and reads them when it wants
+ * to know.  Nothing read from device memory is used as an address before it is compared with
+ * its bound; pointers are searched and compared, or range-checked before a loop runs over them.
+ * Runs (clusters, objects, groups) of more than 512 entries are reduced by a whole wave.
+ *
+ * spt_instance_extents_i64: record int64 [4] = min(obj), max(obj), min(idx), max(idx) (idx
+ *   nullable; INT64_MAX / INT64_MIN where nothing was seen).  The record is initialised here.
+ * spt_merge_instances_i64: pairs re-keyed by (idx[cluster], obj - obj_lo), obj_bits bits for
+ *   the object (1 .. 62; obj_bits + bits(num_parents) <= 63), duplicates of a key become one
+ *   pair with their counts summed, out CSR sorted by (parent, obj): out_pointers int64
+ *   [num_parents + 1], out_obj / out_count / out_y int64 [P] of which the first record[0] are
+ *   written; out_y is that of the LAST pair holding the key.  A parent without a pair gets an
+ *   empty row.  record int64 [4]: [0] merged pairs, [1] parents with at least one pair, [2]
+ *   pairs whose idx lies outside [0, num_parents) (merged into parent 0), [3] pairs that no
+ *   cluster claims or whose obj lies outside [obj_lo, obj_lo + 2^obj_bits) (masked).
+ * spt_pair_stats_i64: per pair a_size (points of its cluster), b_size (points of its object,
+ *   plus cropped_in[pair] when given), iou f32 = (float)count / (float)(a_size + b_size - count),
+ *   one correctly rounded division of the two converted integers; cluster_void [G] (bytes 0 / 1)
+ *   = (float)void points / (float)points > 0.5f with void y < 0 or y >= C; pair_void = void
+ *   object or void cluster; pair_cropped = points of the pair's object lying in void clusters
+ *   (search_void).  kept_iou f32: the IoU of the pair AFTER remove_void(C) - the cluster without
+ *   its void pairs, the object whole - and 0 for a void pair; gt_head: 1 on the last non-void
+ *   pair of each object.  Objects are grouped by one sort of (obj - obj_lo, pair), obj_bits
+ *   1 .. 63 (obj_lo = 0, obj_bits = 63 needs no knowledge of the extents).  Nothing is
+ *   compacted.  status int32 [4]: [0] faults of pointers, [1] obj outside the key range.
+ * spt_panoptic_counts_i64: state [5, C] 8-byte words, 1 <= C <= 32: rows tp, gt_count,
+ *   pred_count int64, rows iou_sum, iou_mod_sum f64.  One pass over the pairs, one over the
+ *   clusters, per-workgroup LDS tables flushed by 64-bit integer atomics.  A pair counts when
+ *   pair_void is 0; gt_count[y] += gt_head; with pred_semantic[cluster] == y: iou > 0.5f
+ *   (strictly) adds to tp and iou_sum, that or stuff_mask[y] to iou_mod_sum; pred_count
+ *   [pred_semantic] += 1 per cluster with cluster_void 0.  The f64 sums are DETERMINISTIC by
+ *   fixed point: each IoU is added as hi * 2^-32 + lo * 2^-64 into two 64-bit integers per sum
+ *   (exact for every f32 in [2^-40, 1], enough for 2^31 pairs), and one f64 add per class and
+ *   call brings them into the state.  status int32 [4]: [0] faults of pointers, [2]
+ *   pred_semantic of a non-void cluster outside [0, C) (not counted), [3] IoUs outside [0, 1]
+ *   (NaN of an empty union; not summed).
+ * spt_weighted_group_mean_f32: out f32 [num_groups, cols] = sum(x[i] * w[i]) / sum(w[i]) over
+ *   the rows with idx[i] == g: products rounded before they are added (no fma), both sums from
+ *   0 in ascending row order, a zero weight sum replaced by 1, one division - the CPU result of
+ *   scatter_mean_weighted bit for bit for groups of up to 512 rows; longer groups: exact f64
+ *   products, 64 strided f64 partial sums, a fixed butterfly, one division and one rounding to
+ *   f32.  status int32 [2]: [0] idx outside [0, num_groups).
+ * ---------------------------------------------------------------------- */
+int spt_instance_extents_i64(const int64_t* obj, int64_t P, const int64_t* idx, int64_t G,
+                             int64_t* record, spt_stream_t stream);
+size_t spt_merge_instances_workspace_bytes(int64_t P, int key_bits);
+int spt_merge_instances_i64(const int64_t* pointers, const int64_t* obj, const int64_t* count,
+                            const int64_t* y, const int64_t* idx, int64_t G, int64_t P,
+                            int64_t num_parents, int64_t obj_lo, int obj_bits,
+                            int64_t* out_pointers, int64_t* out_obj, int64_t* out_count,
+                            int64_t* out_y, int64_t* record, void* ws, size_t ws_bytes,
+                            spt_stream_t stream);
+size_t spt_pair_stats_workspace_bytes(int64_t P, int64_t G, int key_bits);
+int spt_pair_stats_i64(const int64_t* pointers, const int64_t* obj, const int64_t* count,
+                       const int64_t* y, const int64_t* cropped_in, int64_t G, int64_t P, int C,
+                       int64_t obj_lo, int obj_bits, int64_t* a_size, int64_t* b_size, float* iou,
+                       uint8_t* cluster_void, uint8_t* pair_void, int64_t* pair_cropped,
+                       float* kept_iou, uint8_t* gt_head, int32_t* status, void* ws,
+                       size_t ws_bytes, spt_stream_t stream);
+size_t spt_panoptic_counts_workspace_bytes(int C);
+int spt_panoptic_counts_i64(int64_t* state, const int64_t* pred_semantic, const int64_t* pointers,
+                            const int64_t* y, const uint8_t* pair_void, const float* kept_iou,
+                            const uint8_t* gt_head, const uint8_t* cluster_void, int64_t G,
+                            int64_t P, int C, const uint8_t* stuff_mask, int32_t* status, void* ws,
+                            size_t ws_bytes, spt_stream_t stream);
+size_t spt_weighted_group_mean_workspace_bytes(int64_t n, int64_t num_groups);
+int spt_weighted_group_mean_f32(const float* x, int64_t n, int cols, const int64_t* idx,
+                                const float* w, int64_t num_groups, float* out, int32_t* status,
+                                void* ws, size_t ws_bytes, spt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

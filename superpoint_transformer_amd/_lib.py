@@ -271,6 +271,18 @@ SIGNATURES = {
     "spt_rows_accumulate_f32": (_int, [_p, _i64, _p, _p, _i64, _int, _p, _int, _p, _p]),
     "spt_labels_by_index_i64": (_int, [_p, _i64, _p, _i64, _p, _i64, _p, _p, _p, _int, _p, _p, _p]),
     "spt_labels_by_cluster_i64": (_int, [_p, _i64, _p, _p, _p, _i64, _i64, _p, _p, _int, _p, _p, _p]),
+    "spt_instance_extents_i64": (_int, [_p, _i64, _p, _i64, _p, _p]),
+    "spt_merge_instances_workspace_bytes": (_sz, [_i64, _int]),
+    "spt_merge_instances_i64": (_int, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _int, _p, _p, _p, _p,
+                                       _p, _p, _sz, _p]),
+    "spt_pair_stats_workspace_bytes": (_sz, [_i64, _i64, _int]),
+    "spt_pair_stats_i64": (_int, [_p, _p, _p, _p, _p, _i64, _i64, _int, _i64, _int, _p, _p, _p, _p, _p,
+                                  _p, _p, _p, _p, _p, _sz, _p]),
+    "spt_panoptic_counts_workspace_bytes": (_sz, [_int]),
+    "spt_panoptic_counts_i64": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _int, _p, _p, _p,
+                                       _sz, _p]),
+    "spt_weighted_group_mean_workspace_bytes": (_sz, [_i64, _i64]),
+    "spt_weighted_group_mean_f32": (_int, [_p, _i64, _int, _p, _p, _i64, _p, _p, _p, _sz, _p]),
 }
 
 

@@ -99,3 +99,131 @@ class ConfusionMatrix:
         return SimpleNamespace(oa=self.oa(as_percent=as_percent), macc=self.macc(as_percent=as_percent),
                                miou=self.miou(as_percent=as_percent), iou_per_class=iou,
                                seen_class=seen)
+
+
+class PanopticMetricResults:
+    """The fields of the reference's ``PanopticMetricResults`` (src/metrics/panoptic.py:18-42)."""
+    __slots__ = ("pq", "sq", "rq", "pq_modified", "pq_thing", "sq_thing", "rq_thing", "pq_stuff",
+                 "sq_stuff", "rq_stuff", "pq_per_class", "sq_per_class", "rq_per_class",
+                 "precision_per_class", "recall_per_class", "tp_per_class", "fp_per_class",
+                 "fn_per_class", "pq_modified_per_class", "mean_precision", "mean_recall")
+
+
+class PanopticQuality3D:
+    """The reference's ``PanopticQuality3D`` (src/metrics/panoptic.py:45-381) without
+    torchmetrics and without a list of scenes: Panoptic Quality is additive over scenes - objects
+    of different scenes never meet - so the state is five ``[num_classes]`` counters on the
+    device (``panoptic.new_state``), and ``update`` adds a batch into them by
+    ``panoptic.pair_stats`` and ``panoptic.panoptic_counts_`` with no host read.
+
+    ``y`` in ``[0, num_classes)`` are valid labels, anything else is void.  ``compute`` reads the
+    state (and the fault counts of the updates) ONCE and forms every field of
+    ``PanopticMetricResults`` on the host, in float64, with the reference's handling of
+    ``0 / 0``, of unseen classes (``ignore_unseen_classes``) and of ``stuff_classes``.
+
+    ``tp``, ``gt_count``, ``pred_count``, ``iou_sum``, ``iou_mod_sum`` are views of the state:
+    with several ranks, sum them (one all-reduce of ``state`` viewed as its two dtypes)."""
+
+    def __init__(self, num_classes, ignore_unseen_classes=True, stuff_classes=None, device=None):
+        from . import panoptic
+        self.num_classes = int(num_classes)
+        self.ignore_unseen_classes = ignore_unseen_classes
+        self.stuff_classes = [int(c) for c in (stuff_classes if stuff_classes is not None else [])]
+        self._stuff = torch.tensor([c in self.stuff_classes for c in range(self.num_classes)],
+                                   dtype=torch.bool)
+        self.state = panoptic.new_state(self.num_classes, device)
+        self.status = torch.zeros(panoptic.STATUS_WORDS, dtype=torch.int32, device=device)
+        self._stuff_dev = self._stuff.to(self.state.device)
+
+    def to(self, device):
+        self.state = self.state.to(device)
+        self.status = self.status.to(device)
+        self._stuff_dev = self._stuff.to(device)
+        return self
+
+    @property
+    def device(self):
+        return self.state.device
+
+    def _views(self):
+        from . import panoptic
+        return panoptic.state_views(self.state)
+
+    tp = property(lambda self: self._views()[0])
+    gt_count = property(lambda self: self._views()[1])
+    pred_count = property(lambda self: self._views()[2])
+    iou_sum = property(lambda self: self._views()[3])
+    iou_mod_sum = property(lambda self: self._views()[4])
+
+    def reset(self):
+        self.state.zero_()
+        self.status.zero_()
+
+    def update(self, prediction_semantic, instance_data):
+        """``prediction_semantic``: int64 ``[num_clusters]`` labels of the predicted instances;
+        ``instance_data``: their overlaps with ALL target objects of the scene(s), 'stuff'
+        included - predictions and targets are two partitions of the points.  The state follows
+        the inputs' device before the first update."""
+        from . import panoptic
+        from .instance import InstanceData
+        if not isinstance(prediction_semantic, torch.Tensor):
+            raise ValueError("Expected argument `prediction_semantic` to be of type Tensor")
+        if not isinstance(instance_data, InstanceData):
+            raise ValueError("Expected argument `instance_data` to be of type InstanceData")
+        if self.state.device != instance_data.device:
+            self.to(instance_data.device)
+        stats = panoptic.pair_stats(instance_data, self.num_classes, status=self.status)
+        panoptic.panoptic_counts_(self.state, prediction_semantic, instance_data,
+                                  self.num_classes, self._stuff_dev, stats=stats)
+
+    __call__ = update
+
+    def compute(self):
+        from . import panoptic
+        c = self.num_classes
+        words = torch.cat((self.state.view(-1), self.status.long())).tolist()   # THE host read
+        panoptic.raise_status("PanopticQuality3D", words[5 * c:])
+        ints = torch.tensor(words[:3 * c], dtype=torch.int64).view(3, c)
+        sums = torch.tensor(words[3 * c:5 * c], dtype=torch.int64).view(torch.float64).view(2, c)
+        tp, gt_class_counts, pred_class_counts = ints[0], ints[1], ints[2]
+        iou_sum, iou_mod_sum = sums[0], sums[1]
+        is_stuff = self._stuff
+        has_stuff = bool(is_stuff.any())
+
+        precision = tp.double() / pred_class_counts.double()
+        precision[precision.isnan()] = 0
+        recall = tp.double() / gt_class_counts.double()
+        fp = pred_class_counts - tp
+        fn = gt_class_counts - tp
+        sq = iou_sum / tp.double()
+        sq[sq.isnan()] = 0
+        rq = 2 * precision * recall / (precision + recall)
+        rq[rq.isnan()] = 0
+        pq = sq * rq
+        if has_stuff:
+            denominator = (gt_class_counts + pred_class_counts).double() / 2
+            denominator[is_stuff] = gt_class_counts[is_stuff].double()
+            pq_mod = iou_mod_sum / denominator
+        else:
+            pq_mod = pq.clone()
+
+        is_seen = (gt_class_counts + pred_class_counts) > 0
+        default = float("nan") if self.ignore_unseen_classes else 0
+        for t in (pq, sq, rq, pq_mod, precision, recall):
+            t[~is_seen] = default
+        if not self.ignore_unseen_classes:
+            for t in (pq, sq, rq, pq_mod, precision):
+                assert not t.isnan().any()
+
+        nan = torch.tensor(float("nan"), dtype=torch.float64)
+        m = PanopticMetricResults()
+        m.pq, m.sq, m.rq, m.pq_modified = pq.nanmean(), sq.nanmean(), rq.nanmean(), pq_mod.nanmean()
+        m.pq_thing, m.sq_thing, m.rq_thing = (t[~is_stuff].nanmean() for t in (pq, sq, rq))
+        m.pq_stuff, m.sq_stuff, m.rq_stuff = ((t[is_stuff].nanmean() if has_stuff else nan)
+                                              for t in (pq, sq, rq))
+        m.pq_per_class, m.sq_per_class, m.rq_per_class = pq, sq, rq
+        m.precision_per_class, m.recall_per_class = precision, recall
+        m.tp_per_class, m.fp_per_class, m.fn_per_class = tp, fp, fn
+        m.pq_modified_per_class = pq_mod
+        m.mean_precision, m.mean_recall = precision.nanmean(), recall.nanmean()
+        return m

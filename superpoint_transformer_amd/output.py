@@ -15,7 +15,7 @@ import torch
 
 from . import ops, predict
 
-__all__ = ["SemanticSegmentationOutput", "MultiRunInference"]
+__all__ = ["SemanticSegmentationOutput", "MultiRunInference", "PanopticSegmentationOutput"]
 
 log = logging.getLogger(__name__)
 
@@ -270,3 +270,188 @@ class MultiRunInference:
         finally:
             transform.transforms = transform.transforms[1:]
         return self.finalize(output_multi, nag)
+
+
+class PanopticSegmentationOutput(SemanticSegmentationOutput):
+    """A holder for panoptic segmentation model output (src/utils/output_panoptic.py:14-508):
+    the semantic output, the edge affinity logits, the node sizes, optionally the instance
+    targets (``obj``: the level-1 ``InstanceData``, ``obj_edge_index``, ``obj_edge_affinity``,
+    ``pos``, ``obj_pos``) and the predicted instance of each level-1 node (``obj_index_pred``),
+    on the kernels of ``csrc/panoptic.hip`` (``panoptic``) and ``csrc/predict.hip``.
+
+    Differences from the reference:
+      * ``obj_index_pred`` as a list of multi-setting partition results
+        (``PartitionParameterSearchStorage``) is not supported and raises;
+      * ``num_edges`` is ``edge_affinity_logits.shape[0]`` (the reference reads ``shape[1]`` of
+        the 1-D tensor its own ``debug`` asserts);
+      * an instance's label is the first maximum of its mean logits (``predict.row_argmax``),
+        where the reference takes the maximum of their softmax: the two differ only where
+        rounding in the softmax creates a tie the logits do not have;
+      * the per-voxel and per-point ``InstanceData`` are built directly - one pair per point,
+        ``count == 1`` - and a hop given as ``sub`` is walked as stored."""
+
+    def __init__(self, logits, stuff_classes, edge_affinity_logits, node_size, y_hist=None,
+                 obj=None, obj_edge_index=None, obj_edge_affinity=None, pos=None, obj_pos=None,
+                 obj_index_pred=None, semantic_loss=None, edge_affinity_loss=None):
+        device = edge_affinity_logits.device
+        self.stuff_classes = torch.tensor(stuff_classes, device=device).long() \
+            if stuff_classes is not None else torch.empty(0, device=device).long()
+        self.edge_affinity_logits = edge_affinity_logits
+        self.node_size = node_size
+        self.obj = obj
+        self.obj_edge_index = obj_edge_index
+        self.obj_edge_affinity = obj_edge_affinity
+        self.pos = pos
+        self.obj_pos = obj_pos
+        self.obj_index_pred = obj_index_pred
+        self.semantic_loss = semantic_loss
+        self.edge_affinity_loss = edge_affinity_loss
+        self._num_obj_pred = None
+        super().__init__(logits, y_hist=y_hist)
+        if self.has_multi_instance_pred:
+            raise NotImplementedError(
+                "obj_index_pred as a list of multi-setting partition results is not supported: "
+                "pass the [num_nodes] index tensor of one setting")
+        self.debug()
+
+    def debug(self):
+        super().debug()
+        assert self.edge_affinity_logits.dim() == 1
+        assert self.node_size.dim() == 1
+        assert self.node_size.shape[0] == self.num_nodes
+        if self.has_instance_pred:
+            assert self.obj_index_pred.dim() == 1
+            assert self.obj_index_pred.shape[0] == self.num_nodes
+        items = [self.obj_edge_index, self.obj_edge_affinity, self.pos, self.obj_pos]
+        if all(x is None for x in items):
+            return
+        assert all(x is not None for x in items)
+        from .instance import InstanceData
+        assert isinstance(self.obj, InstanceData)
+        assert self.obj.num_clusters == self.num_nodes
+        assert self.obj_edge_index.dim() == 2
+        assert self.obj_edge_index.shape[0] == 2
+        assert self.obj_edge_index.shape[1] == self.num_edges
+        assert self.obj_edge_affinity.dim() == 1
+        assert self.obj_edge_affinity.shape[0] == self.num_edges
+
+    @property
+    def has_target(self):
+        """Whether ``self`` holds the targets of panoptic segmentation."""
+        items = [self.obj, self.obj_edge_index, self.obj_edge_affinity, self.pos, self.obj_pos]
+        return super().has_target and all(x is not None for x in items)
+
+    @property
+    def has_instance_pred(self):
+        return self.obj_index_pred is not None
+
+    @property
+    def has_multi_instance_pred(self):
+        return self.has_instance_pred and not isinstance(self.obj_index_pred, torch.Tensor)
+
+    @property
+    def num_edges(self):
+        return self.edge_affinity_logits.shape[0]
+
+    @property
+    def edge_affinity_pred(self):
+        """The sigmoid of ``edge_affinity_logits``: what the graph clustering takes."""
+        return self.edge_affinity_logits.sigmoid()
+
+    @property
+    def void_edge_mask(self):
+        """Mask of the edges connecting two void nodes (``None`` without a target)."""
+        if not self.has_target:
+            return
+        mask = self.void_mask[self.obj_edge_index]
+        return mask[0] & mask[1]
+
+    def sanitized_edge_affinities(self):
+        """``(edge_affinity_logits, obj_edge_affinity, is_same_class, is_same_obj)`` without the
+        edges connecting two void nodes."""
+        idx = torch.where(~self.void_edge_mask)[0]
+        obj, count, y = self.obj.major(num_classes=self.num_classes)
+        is_same_class = y[self.obj_edge_index[0]] == y[self.obj_edge_index[1]]
+        is_same_obj = obj[self.obj_edge_index[0]] == obj[self.obj_edge_index[1]]
+        return self.edge_affinity_logits[idx], self.obj_edge_affinity[idx], \
+            is_same_class[idx], is_same_obj[idx]
+
+    def _num_obj(self):
+        if self._num_obj_pred is None:
+            self._num_obj_pred = int(self.obj_index_pred.max()) + 1     # a host read, once
+        return self._num_obj_pred
+
+    def weighted_instance_semantic_pred(self, check=True):
+        """``(obj_y, obj_semantic_score, obj_logits)`` of the predicted instances: the mean of
+        their nodes' level-1 logits weighted by the node sizes (``panoptic.weighted_group_mean``),
+        its first maximum and the maximum of its softmax (``panoptic.semantic_score``)."""
+        if not self.has_instance_pred:
+            return None, None, None
+        from . import panoptic
+        obj_logits = panoptic.weighted_group_mean(self._level1.detach().float(),
+                                                  self.obj_index_pred, self.node_size,
+                                                  self._num_obj(), check=check)
+        obj_y = predict.row_argmax(obj_logits)
+        obj_semantic_score = panoptic.semantic_score(obj_logits)
+        return obj_y, obj_semantic_score, obj_logits
+
+    def panoptic_pred(self, check=True):
+        """``(obj_score, obj_y, instance_data)`` of the predicted instances; ``instance_data``
+        is ``obj`` merged by ``obj_index_pred`` (``panoptic.merge_instances``), ``None`` without
+        a target."""
+        if not self.has_instance_pred:
+            return None, None, None
+        instance_data = None
+        if self.has_target:
+            from . import panoptic
+            instance_data = panoptic.merge_instances(self.obj, self.obj_index_pred,
+                                                     num_parents=self._num_obj_pred)
+            self._num_obj_pred = instance_data.num_groups
+        obj_y, obj_semantic_score, _ = self.weighted_instance_semantic_pred(check=check)
+        return obj_semantic_score, obj_y, instance_data
+
+    def _superpoint_labels(self, check):
+        obj_y = self.weighted_instance_semantic_pred(check=check)[0]
+        return predict.labels_through(obj_y, [self.obj_index_pred], want=("voxel",),
+                                      check=check)["voxel"]
+
+    @staticmethod
+    def _per_point(index, y, count=None):
+        from .instance import InstanceData
+        n = index.shape[0]
+        if count is None:
+            count = torch.ones(n, dtype=torch.long, device=index.device)
+        return InstanceData(torch.arange(n + 1, device=index.device), index, count, y)
+
+    def superpoint_panoptic_pred(self, check=True):
+        """``(sp_y, obj_index_pred, sp_obj_pred)``: the instances' labels on the level-1 nodes and
+        the node-wise ``InstanceData`` carrying the predictions (``count`` = the node sizes)."""
+        sp_y = self._superpoint_labels(check)
+        return sp_y, self.obj_index_pred, self._per_point(self.obj_index_pred, sp_y,
+                                                          self.node_size)
+
+    def voxel_panoptic_pred(self, super_index=None, sub=None, check=True):
+        """``(vox_y, vox_index, vox_obj_pred)``: label and instance of each level-0 point,
+        through ``super_index`` or ``sub``, and the voxel-wise ``InstanceData`` (one pair per
+        voxel, ``count == 1``)."""
+        assert super_index is not None or sub is not None, \
+            "Must provide either `super_index` or `sub`"
+        hop = [super_index if super_index is not None else sub]
+        vox_y = predict.labels_through(self._superpoint_labels(check), hop, want=("voxel",),
+                                       check=check)["voxel"]
+        vox_index = predict.labels_through(self.obj_index_pred, hop, want=("voxel",),
+                                           check=check)["voxel"]
+        return vox_y, vox_index, self._per_point(vox_index, vox_y)
+
+    def full_res_panoptic_pred(self, super_index_level0_to_level1=None,
+                               super_index_raw_to_level0=None, sub_level1_to_level0=None,
+                               sub_level0_to_raw=None, check=True):
+        """``(raw_y, raw_index, raw_obj_pred)``: the same on the full-resolution cloud, each of
+        the two hops as a ``super_index`` tensor or the ``sub`` Cluster of the level above."""
+        hops = self._full_res_hops(super_index_level0_to_level1, super_index_raw_to_level0,
+                                   sub_level1_to_level0, sub_level0_to_raw)
+        raw_y = predict.labels_through(self._superpoint_labels(check), hops, want=("raw",),
+                                       check=check)["raw"]
+        raw_index = predict.labels_through(self.obj_index_pred, hops, want=("raw",),
+                                           check=check)["raw"]
+        return raw_y, raw_index, self._per_point(raw_index, raw_y)
