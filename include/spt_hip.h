@@ -1392,6 +1392,33 @@ int spt_hist_loss_fwd_f32(const float* logits, const int64_t* target, int64_t ro
 int spt_hist_loss_bwd_f32(const float* logits, const int64_t* target, int64_t rows, int C, int ncols,
                           int mode, int64_t ignore_index, const float* weight, const float* gout,
                           const double* den, float* glogits, spt_stream_t stream);
+/* Edge-affinity loss of the panoptic model (PanopticSegmentationModule.model_step,
+ * src/models/panoptic.py:726-796): BCE with logits of logits f32 [E] against target f32 [E] over
+ * the edges (i, j) = edge_index int64 [2, E] with keep = !(node_void[i] && node_void[j]); nothing
+ * is compacted.  Per kept edge: kind = 2 (node_y[i] != node_y[j]) + (node_obj[i] != node_obj[j]),
+ * w = case_weight[kind] (f32 [4]; NULL: 1), pw = pos_weight[0] (a DEVICE scalar; NULL: 1),
+ *   l = (1 - t) x + (1 + (pw - 1) t) (max(-x, 0) + log1p(exp(-|x|)))      evaluated in f64.
+ *   fwd: loss[1] f32 = sum w l / sum w, den[1] f64 = sum w (without a table: the number of kept
+ *        edges, the loss their mean).  No kept edge: 0 / 0 = NaN.  f64 partial sums per workgroup
+ *        added in a fixed order: bitwise reproducible.  ws: spt_edge_affinity_loss_workspace_bytes.
+ *        stats (may be NULL) int64 [4] += tp, fp, tn, fn of (x > 0) against (t > 0.5) over the
+ *        kept edges.  status (may be NULL) int32 [1] += edges with an end outside [0, N): dropped.
+ *   bwd: glogits[e] = gout[0] w / den[0] ((1 + (pw - 1) t) sigmoid(x) - pw t) for a kept edge
+ *        (= (1 - t) - (1 + (pw - 1) t) sigmoid(-x), in the form torch's backward evaluates),
+ *        an explicit 0 for a dropped one.  gout / den are device scalars. */
+size_t spt_edge_affinity_loss_workspace_bytes(int64_t E);
+int spt_edge_affinity_loss_fwd_f32(const float* logits, const float* target,
+                                   const int64_t* edge_index, int64_t E, const uint8_t* node_void,
+                                   const int64_t* node_obj, const int64_t* node_y, int64_t N,
+                                   const float* case_weight, const float* pos_weight, float* loss,
+                                   double* den, int64_t* stats, int32_t* status, void* ws,
+                                   size_t ws_bytes, spt_stream_t stream);
+int spt_edge_affinity_loss_bwd_f32(const float* logits, const float* target,
+                                   const int64_t* edge_index, int64_t E, const uint8_t* node_void,
+                                   const int64_t* node_obj, const int64_t* node_y, int64_t N,
+                                   const float* case_weight, const float* pos_weight,
+                                   const float* gout, const double* den, float* glogits,
+                                   spt_stream_t stream);
 /* Confusion matrix from segment-level predictions and label histograms, without flattening them
  * to points (ConfusionMatrix.update, src/metrics/semantic.py:66-107): confmat[t, pred[r]] +=
  * h[r, t] for t < C <= 32 (target int64 [rows, ncols >= C]; columns past C are void), or, with
@@ -1646,6 +1673,28 @@ size_t spt_weighted_group_mean_workspace_bytes(int64_t n, int64_t num_groups);
 int spt_weighted_group_mean_f32(const float* x, int64_t n, int cols, const int64_t* idx,
                                 const float* w, int64_t num_groups, float* out, int32_t* status,
                                 void* ws, size_t ws_bytes, spt_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Panoptic criterion: major objects                            (csrc/panoptic.hip)
+ * InstanceData.major(num_classes) (src/data/instance.py:162-225) without a host read.
+ *
+ * spt_instance_major_i64: out_obj / out_count / out_y int64 [G], per cluster the pair of the
+ *   largest count - ties to the lowest pair index.  A pair is void with y < 0 or y >= C.  If ANY
+ *   cluster whose largest pair is void holds it with (float)count / (float)total <= 0.5f (one f32
+ *   division of the converted integers; NaN counts as "not above"), EVERY cluster whose largest
+ *   pair is void takes the pair of the largest count * ~void instead (ties to the lowest index; an
+ *   all-void cluster takes its first pair with count 0) - as the reference's masked assignment
+ *   behaves.  The decision stays a device flag: kernel 1 writes both candidates and ORs the flag,
+ *   kernel 2 selects.  One lane per cluster, a whole wave for clusters of more than 64 pairs.
+ *   status int32 [2], ADDED to: [0] clusters without a pair (the reference indexes out of range;
+ *   here obj = -1, count = 0, y = -1), [1] faults of pointers (such a cluster is treated as
+ *   empty).  Every access stays in bounds whatever the data.  G and P in 1 .. 2^31 - 2.
+ * ---------------------------------------------------------------------- */
+size_t spt_instance_major_workspace_bytes(int64_t G);
+int spt_instance_major_i64(const int64_t* pointers, const int64_t* obj, const int64_t* count,
+                           const int64_t* y, int64_t G, int64_t P, int C, int64_t* out_obj,
+                           int64_t* out_count, int64_t* out_y, int32_t* status, void* ws,
+                           size_t ws_bytes, spt_stream_t stream);
 
 #ifdef __cplusplus
 }

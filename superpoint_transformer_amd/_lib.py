@@ -283,6 +283,12 @@ SIGNATURES = {
                                        _sz, _p]),
     "spt_weighted_group_mean_workspace_bytes": (_sz, [_i64, _i64]),
     "spt_weighted_group_mean_f32": (_int, [_p, _i64, _int, _p, _p, _i64, _p, _p, _p, _sz, _p]),
+    "spt_instance_major_workspace_bytes": (_sz, [_i64]),
+    "spt_instance_major_i64": (_int, [_p, _p, _p, _p, _i64, _i64, _int, _p, _p, _p, _p, _p, _sz, _p]),
+    "spt_edge_affinity_loss_workspace_bytes": (_sz, [_i64]),
+    "spt_edge_affinity_loss_fwd_f32": (_int, [_p, _p, _p, _i64, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _p,
+                                              _p, _sz, _p]),
+    "spt_edge_affinity_loss_bwd_f32": (_int, [_p, _p, _p, _i64, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _p]),
 }
 
 

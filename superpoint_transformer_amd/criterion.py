@@ -1,4 +1,6 @@
-"""The semantic criterion of the reference's default configuration, on the histogram-loss kernels.
+"""The criteria of the reference's default configurations: the semantic criterion on the
+histogram-loss kernels, and the panoptic one - semantic loss plus the edge-affinity loss - on
+``ops.edge_affinity_loss`` (``EdgeAffinityCriterion``, ``PanopticCriterion``, below).
 
 ``configs/model/semantic/default.yaml:7-12`` trains with ``loss_type: 'ce_kl'``,
 ``weighted_loss: True`` and ``multi_stage_loss_lambdas: [1, 50]`` on the per-superpoint label
@@ -83,3 +85,87 @@ class SemanticCriterion(torch.nn.Module):
             else:
                 loss = loss + lamb * self._level("ce" if self.loss_type == "ce" else "kl", a, b, cm)
         return loss
+
+
+class EdgeAffinityCriterion(torch.nn.Module):
+    """The edge-affinity criterion of ``PanopticSegmentationModule.model_step``
+    (src/models/panoptic.py:726-796), applied to what ``sanitized_edge_affinities()`` keeps -
+    without compacting: ``criterion(logits, target, obj_edge_index, node_void, node_obj, node_y)``
+    or ``criterion(output)`` with a ``PanopticSegmentationOutput`` that has a target (its major
+    objects then come from ``panoptic.major_objects``, its void mask from ``predict.void_mask``).
+
+    ``weighted=False``: ``BCEWithLogitsLoss`` of src/loss/bce.py, the configs' default - the
+    weights are ignored, the mean over the kept edges.  ``weighted=True``:
+    ``WeightedBCEWithLogitsLoss``, ``sum(w l) / sum(w)`` with ``w`` the entry of ``case_weights``
+    for ``[same-class same-obj, same-class diff-obj, diff-class same-obj, diff-class diff-obj]``
+    of the end nodes' major objects; ``case_weights`` that is ``None`` or not of length 4 means no
+    weighting (``_edge_affinity_weights``).  A void ``y`` takes part in the class comparison by
+    its value, as in the reference.  ``pos_weight``: a number, kept as a buffer and read on the
+    device.  ``stats=``: an int64 ``[4]`` buffer (``metrics.BinaryEdgeStats.state``) that takes
+    tp / fp / tn / fn of the kept edges from the same pass.  Nothing waits on the host."""
+
+    def __init__(self, weighted=False, case_weights=None, pos_weight=None):
+        super().__init__()
+        self.weighted = bool(weighted)
+        self.register_buffer("case_weights", None)
+        self.register_buffer("pos_weight", None)
+        if case_weights is not None and len(case_weights) == 4:
+            self.case_weights = torch.as_tensor(case_weights, dtype=torch.float32).reshape(4)
+        if pos_weight is not None:
+            self.pos_weight = torch.as_tensor(pos_weight, dtype=torch.float32).reshape(1)
+
+    def extra_repr(self):
+        return f"weighted={self.weighted}"
+
+    @staticmethod
+    def targets_of(output):
+        """``(node_void, node_obj, node_y)`` of a ``PanopticSegmentationOutput`` with a target."""
+        from . import panoptic
+        if not output.has_target:
+            raise ValueError("the output holds no target: y_hist, obj, obj_edge_index, "
+                             "obj_edge_affinity, pos and obj_pos are all needed")
+        obj, _, y = panoptic.major_objects(output.obj, output.num_classes)
+        return output.void_mask, obj, y
+
+    def forward(self, logits, target=None, obj_edge_index=None, node_void=None, node_obj=None,
+                node_y=None, stats=None):
+        if not torch.is_tensor(logits):
+            output = logits
+            node_void, node_obj, node_y = self.targets_of(output)
+            logits, target = output.edge_affinity_logits, output.obj_edge_affinity
+            obj_edge_index = output.obj_edge_index
+        cw = self.case_weights if self.weighted else None
+        pw = self.pos_weight
+        dev = logits.device
+        if cw is not None and cw.device != dev:
+            cw = cw.to(dev)
+        if pw is not None and pw.device != dev:
+            pw = pw.to(dev)
+        return ops.edge_affinity_loss(logits, target, obj_edge_index, node_void, node_obj, node_y,
+                                      case_weights=cw, pos_weight=pw, stats=stats)
+
+
+class PanopticCriterion(torch.nn.Module):
+    """``loss = semantic_loss + edge_affinity_loss_lambda * edge_affinity_loss``
+    (``model_step``, src/models/panoptic.py:760-796): ``semantic`` a ``SemanticCriterion``,
+    ``edge_affinity`` an ``EdgeAffinityCriterion``.  Returns ``(loss, semantic_loss,
+    edge_affinity_loss)``.  ``confmat=`` goes to the semantic criterion, ``stats=`` to the
+    edge-affinity criterion."""
+
+    def __init__(self, semantic, edge_affinity, edge_affinity_loss_lambda=1):
+        super().__init__()
+        self.semantic = semantic
+        self.edge_affinity = edge_affinity
+        self.edge_affinity_loss_lambda = float(edge_affinity_loss_lambda)
+
+    def extra_repr(self):
+        return f"edge_affinity_loss_lambda={self.edge_affinity_loss_lambda}"
+
+    def forward(self, logits, y_hist, edge_affinity_logits, obj_edge_affinity, obj_edge_index,
+                node_void, node_obj, node_y, confmat=None, stats=None):
+        semantic_loss = self.semantic(logits, y_hist, confmat=confmat)
+        edge_affinity_loss = self.edge_affinity(edge_affinity_logits, obj_edge_affinity,
+                                                obj_edge_index, node_void, node_obj, node_y,
+                                                stats=stats)
+        loss = semantic_loss + self.edge_affinity_loss_lambda * edge_affinity_loss
+        return loss, semantic_loss, edge_affinity_loss

@@ -7,6 +7,7 @@
 // nll_loss forward / backward reduce with a single workgroup (0.26-0.42 ms per call at 428 571
 // rows, profiles/r02z).  Sums are accumulated in f64 per workgroup and added up in a fixed order
 // by a second kernel: deterministic.
+#include <limits.h>
 #include <math.h>
 
 #include <algorithm>
@@ -353,9 +354,174 @@ __global__ __launch_bounds__(CE_BLOCK) void confusion_kernel(
     if (s_cm[i]) atomicAdd(reinterpret_cast<unsigned long long*>(confmat) + i, s_cm[i]);
 }
 
+// ---- edge-affinity loss of the panoptic model (src/models/panoptic.py:760-796) -------------------
+//
+// BCE with logits over the edges of obj_edge_index that do not join two void nodes, optionally
+// weighted by the edge's case (same / different class x same / different object of the end nodes'
+// major objects) and by pos_weight.  One pass: the keep mask, the case, the weight, the term and
+// the tp / fp / tn / fn of `x > 0` against `t > 0.5` per edge; nothing is compacted.  The term is
+// evaluated in f64 (exp, log1p), so the sum carries no error of an f32 transcendental; partial
+// sums per workgroup in f64, added in a fixed order by ce_finish_kernel<double>: deterministic.
+constexpr int EA_BLOCK = 256;
+
+struct EdgeCase {
+  bool keep;       // both ends in range and not both void
+  bool bad;        // an end outside [0, N)
+  int kind;        // 2 * (y_i != y_j) + (obj_i != obj_j)
+};
+
+__device__ __forceinline__ EdgeCase edge_case(const int64_t* __restrict__ ei, int64_t E, int64_t e,
+                                              const uint8_t* __restrict__ node_void,
+                                              const int64_t* __restrict__ node_obj,
+                                              const int64_t* __restrict__ node_y, int64_t N) {
+  EdgeCase c = {false, false, 0};
+  const int64_t i = ei[e], j = ei[E + e];
+  if (i < 0 || i >= N || j < 0 || j >= N) {    // compared with the bound before it indexes a table
+    c.bad = true;
+    return c;
+  }
+  c.keep = !(node_void[i] && node_void[j]);
+  c.kind = 2 * (node_y[i] != node_y[j]) + (node_obj[i] != node_obj[j]);
+  return c;
+}
+
+__global__ __launch_bounds__(EA_BLOCK) void ea_fwd_kernel(
+    const float* __restrict__ logits, const float* __restrict__ target,
+    const int64_t* __restrict__ ei, int64_t E, const uint8_t* __restrict__ node_void,
+    const int64_t* __restrict__ node_obj, const int64_t* __restrict__ node_y, int64_t N,
+    const float* __restrict__ case_weight, const float* __restrict__ pos_weight,
+    double* __restrict__ partial, int64_t* __restrict__ stats, int32_t* __restrict__ status) {
+  __shared__ double s_num[EA_BLOCK / 64], s_den[EA_BLOCK / 64];
+  __shared__ int s_st[4][EA_BLOCK / 64];
+  const int64_t e = (int64_t)blockIdx.x * EA_BLOCK + threadIdx.x;
+  const double pw = pos_weight ? (double)pos_weight[0] : 1.0;
+  double num = 0.0, den = 0.0;
+  int what = -1;                               // 0 tp, 1 fp, 2 tn, 3 fn of a kept edge
+  if (e < E) {
+    const EdgeCase c = edge_case(ei, E, e, node_void, node_obj, node_y, N);
+    if (c.bad && status) atomicAdd(&status[0], 1);
+    if (c.keep) {
+      const float xf = logits[e], tf = target[e];
+      const double x = (double)xf, t = (double)tf;
+      const double w = case_weight ? (double)case_weight[c.kind] : 1.0;
+      // torch's stable form of BCE with logits
+      const double l = (1.0 - t) * x +
+                       (1.0 + (pw - 1.0) * t) * (fmax(-x, 0.0) + log1p(exp(-fabs(x))));
+      num = w * l;
+      den = w;
+      what = (xf > 0.f) ? (tf > 0.5f ? 0 : 1) : (tf > 0.5f ? 3 : 2);
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    num += __shfl_xor(num, o, 64);
+    den += __shfl_xor(den, o, 64);
+  }
+  const int wave = threadIdx.x >> 6;
+  if (stats) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int n = __popcll(__ballot(what == k));
+      if ((threadIdx.x & 63) == 0) s_st[k][wave] = n;
+    }
+  }
+  if ((threadIdx.x & 63) == 0) {
+    s_num[wave] = num;
+    s_den[wave] = den;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double a = 0.0, b = 0.0;
+    for (int w = 0; w < EA_BLOCK / 64; ++w) {
+      a += s_num[w];
+      b += s_den[w];
+    }
+    partial[2 * (size_t)blockIdx.x] = a;
+    partial[2 * (size_t)blockIdx.x + 1] = b;
+  }
+  if (stats && threadIdx.x < 4) {              // integer sums: any arrival order gives the same
+    int n = 0;
+    for (int w = 0; w < EA_BLOCK / 64; ++w) n += s_st[threadIdx.x][w];
+    if (n) atomicAdd(reinterpret_cast<unsigned long long*>(stats) + threadIdx.x, (unsigned long long)n);
+  }
+}
+
+__global__ __launch_bounds__(EA_BLOCK) void ea_bwd_kernel(
+    const float* __restrict__ logits, const float* __restrict__ target,
+    const int64_t* __restrict__ ei, int64_t E, const uint8_t* __restrict__ node_void,
+    const int64_t* __restrict__ node_obj, const int64_t* __restrict__ node_y, int64_t N,
+    const float* __restrict__ case_weight, const float* __restrict__ pos_weight,
+    const float* __restrict__ gout, const double* __restrict__ den, float* __restrict__ glogits) {
+  const int64_t e = (int64_t)blockIdx.x * EA_BLOCK + threadIdx.x;
+  if (e >= E) return;
+  const EdgeCase c = edge_case(ei, E, e, node_void, node_obj, node_y, N);
+  float g = 0.f;                               // a dropped edge: an explicit 0, never 0 * (1 / den)
+  if (c.keep) {
+    const double pw = pos_weight ? (double)pos_weight[0] : 1.0;
+    const double x = (double)logits[e], t = (double)target[e];
+    const double w = case_weight ? (double)case_weight[c.kind] : 1.0;
+    // (1 - t) - (1 + (pw - 1) t) sigmoid(-x) in the form torch's own backward evaluates,
+    // (1 + (pw - 1) t) sigmoid(x) - pw t: nothing cancels where sigmoid(x) vanishes
+    const double sig = 1.0 / (1.0 + exp(-x));  // exp(-x) = inf gives 0
+    g = (float)((double)gout[0] * w / den[0] * ((1.0 + (pw - 1.0) * t) * sig - pw * t));
+  }
+  glogits[e] = g;
+}
+
 }  // namespace spt
 
 using namespace spt;
+
+extern "C" size_t spt_edge_affinity_loss_workspace_bytes(int64_t E) {
+  if (E < 1 || E >= (int64_t)INT32_MAX * EA_BLOCK) return 0;
+  return (size_t)ceil_div(E, (int64_t)EA_BLOCK) * 2 * sizeof(double);
+}
+
+static bool ea_sizes_ok(int64_t E, int64_t N) {
+  return E >= 1 && E < (int64_t)INT32_MAX * EA_BLOCK && N >= 1;
+}
+
+// loss[0] = sum w l / sum w over the kept edges (w = case_weight[case], or 1 without a table: the
+// mean), den[0] = sum w as f64; no kept edge: 0 / 0 = NaN.  stats (optional) int64 [4] += tp, fp,
+// tn, fn of (logit > 0) against (target > 0.5) over the kept edges; status (optional) int32 [1] +=
+// edges with an end outside [0, N), which are dropped.
+extern "C" int spt_edge_affinity_loss_fwd_f32(
+    const float* logits, const float* target, const int64_t* edge_index, int64_t E,
+    const uint8_t* node_void, const int64_t* node_obj, const int64_t* node_y, int64_t N,
+    const float* case_weight, const float* pos_weight, float* loss, double* den, int64_t* stats,
+    int32_t* status, void* ws, size_t ws_bytes, spt_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SPT_CHECK_ARG(ea_sizes_ok(E, N), "E >= 1 and N >= 1");
+  SPT_CHECK_ARG(logits && target && edge_index && node_void && node_obj && node_y && loss && den,
+                "null pointer");
+  SPT_CHECK_ARG(ws && ws_bytes >= spt_edge_affinity_loss_workspace_bytes(E), "workspace too small");
+  const int nblocks = (int)ceil_div(E, (int64_t)EA_BLOCK);
+  double* partial = (double*)ws;
+  ea_fwd_kernel<<<nblocks, EA_BLOCK, 0, stream>>>(logits, target, edge_index, E, node_void,
+                                                  node_obj, node_y, N, case_weight, pos_weight,
+                                                  partial, stats, status);
+  ce_finish_kernel<double><<<1, 256, 0, stream>>>(partial, nblocks, loss, den);
+  SPT_CHECK_LAUNCH();
+  return 0;
+}
+
+// glogits[e] = gout[0] w / den[0] ((1 + (pw - 1) t) sigmoid(x) - pw t) for a kept edge, 0 for
+// a dropped one (also when den is 0 or NaN).  gout, den, pos_weight are DEVICE scalars.
+extern "C" int spt_edge_affinity_loss_bwd_f32(
+    const float* logits, const float* target, const int64_t* edge_index, int64_t E,
+    const uint8_t* node_void, const int64_t* node_obj, const int64_t* node_y, int64_t N,
+    const float* case_weight, const float* pos_weight, const float* gout, const double* den,
+    float* glogits, spt_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SPT_CHECK_ARG(ea_sizes_ok(E, N), "E >= 1 and N >= 1");
+  SPT_CHECK_ARG(logits && target && edge_index && node_void && node_obj && node_y && gout && den &&
+                    glogits, "null pointer");
+  const int nblocks = (int)ceil_div(E, (int64_t)EA_BLOCK);
+  ea_bwd_kernel<<<nblocks, EA_BLOCK, 0, stream>>>(logits, target, edge_index, E, node_void,
+                                                  node_obj, node_y, N, case_weight, pos_weight,
+                                                  gout, den, glogits);
+  SPT_CHECK_LAUNCH();
+  return 0;
+}
 
 extern "C" size_t spt_cross_entropy_workspace_bytes(int64_t rows) {
   return (size_t)(ceil_div(rows > 0 ? rows : 1, (int64_t)CE_BLOCK)) * 2 * sizeof(double);

@@ -1,7 +1,8 @@
 // Panoptic evaluation on the device (include/spt_hip.h, "Panoptic evaluation"): merging the
 // cluster-object overlaps of a level into predicted instances, the per-pair sizes / IoUs / void
 // masks, the five per-class counters of PanopticQuality3D, and the weighted group mean behind
-// the instances' semantic logits.
+// the instances' semantic logits; and, for the panoptic criterion, the major object of every
+// cluster (InstanceData.major) with its data-dependent branch kept on the device.
 //
 // Grouping is always ONE stable radix sort of a key as wide as its extents need (low word, then
 // high word, as csrc/voxel.hip), run heads through the device scan, and integer run sums: no
@@ -529,6 +530,136 @@ __global__ __launch_bounds__(THREADS) void weighted_mean_kernel(
   }
 }
 
+// ---- major objects (InstanceData.major, src/data/instance.py:162-225) ------------------------------
+// status of spt_instance_major_i64 (int32 words)
+enum { MJ_EMPTY = 0, MJ_POINTERS = 1 };
+constexpr int MAJOR_WAVE = 64;     // clusters of more pairs than this are searched by a whole wave
+
+// the largest value, and among equal values the lowest pair index (scatter_max on the CPU)
+struct Best {
+  int64_t c, j;
+};
+__device__ __forceinline__ void take_best(Best& b, int64_t c, int64_t j) {
+  if (c > b.c || (c == b.c && j < b.j)) {
+    b.c = c;
+    b.j = j;
+  }
+}
+
+// Kernel 1: both candidates of every cluster - the pair of the largest count (into the outputs)
+// and the pair of the largest count * ~void (into scratch) - and the flag "some cluster whose
+// largest pair is void holds it with count / total <= 0.5 (as f32)".
+__global__ __launch_bounds__(THREADS) void major_candidates_kernel(
+    const int64_t* __restrict__ pointers, const int64_t* __restrict__ obj,
+    const int64_t* __restrict__ count, const int64_t* __restrict__ y, int64_t G, int64_t P, int C,
+    int64_t* __restrict__ out_obj, int64_t* __restrict__ out_count, int64_t* __restrict__ out_y,
+    int64_t* __restrict__ nv_obj, int64_t* __restrict__ nv_count, int64_t* __restrict__ nv_y,
+    int32_t* __restrict__ flag, int32_t* __restrict__ status) {
+  const int lane = threadIdx.x & 63;
+  if (blockIdx.x == 0 && threadIdx.x == 0 && (pointers[0] != 0 || pointers[G] != P))
+    atomicAdd(&status[MJ_POINTERS], 1);
+  auto load = [&](int64_t j, Best& m, Best& n, int64_t& total) {
+    const int64_t c = count[j], l = y[j];
+    total += c;
+    take_best(m, c, j);
+    take_best(n, (l < 0 || l >= C) ? 0 : c, j);
+  };
+  // writes both candidates of cluster v; true when v raises the flag
+  auto finish = [&](int64_t v, const Best& m, const Best& n, int64_t total) -> bool {
+    if (m.j < 0 || m.j >= P || n.j < 0 || n.j >= P) {      // no pair: nothing to index
+      out_obj[v] = nv_obj[v] = -1;
+      out_count[v] = nv_count[v] = 0;
+      out_y[v] = nv_y[v] = -1;
+      return false;
+    }
+    const int64_t ym = y[m.j];
+    out_obj[v] = obj[m.j];
+    out_count[v] = m.c;
+    out_y[v] = ym;
+    nv_obj[v] = obj[n.j];
+    nv_count[v] = n.c;
+    nv_y[v] = y[n.j];
+    // (0 / 0 = NaN is not above one half either)
+    return (ym < 0 || ym >= C) && !((float)m.c / (float)total > 0.5f);
+  };
+  bool up = false;
+  const int64_t stride = (int64_t)gridDim.x * THREADS;
+  for (int64_t base = (int64_t)blockIdx.x * THREADS + (threadIdx.x & ~63); base < G;
+       base += stride) {                                      // wave-uniform trip count
+    const int64_t v = base + lane;
+    int64_t b = 0, e = 0;
+    const bool valid = v < G;
+    if (valid) {
+      b = pointers[v];
+      e = pointers[v + 1];
+      if (!(0 <= b && b <= e && e <= P)) {
+        atomicAdd(&status[MJ_POINTERS], 1);
+        b = e = 0;
+      } else if (b == e) {
+        atomicAdd(&status[MJ_EMPTY], 1);                       // the reference indexes out of range
+      }
+    }
+    const bool longrun = valid && e - b > MAJOR_WAVE;
+    if (valid && !longrun) {
+      Best m = {INT64_MIN, INT64_MAX}, n = {INT64_MIN, INT64_MAX};
+      int64_t total = 0;
+      for (int64_t j = b; j < e; ++j) load(j, m, n, total);
+      up = finish(v, m, n, total) || up;
+    }
+    uint64_t todo = __ballot(longrun);
+    while (todo) {
+      const int src = __ffsll((unsigned long long)todo) - 1;
+      todo &= todo - 1;
+      const int64_t b2 = __shfl(b, src, 64), e2 = __shfl(e, src, 64), v2 = __shfl(v, src, 64);
+      Best m = {INT64_MIN, INT64_MAX}, n = {INT64_MIN, INT64_MAX};
+      int64_t total = 0;
+      for (int64_t j = b2 + lane; j < e2; j += 64) load(j, m, n, total);
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        total += __shfl_xor(total, o, 64);                     // integers: order-free
+        take_best(m, __shfl_xor(m.c, o, 64), __shfl_xor(m.j, o, 64));
+        take_best(n, __shfl_xor(n.c, o, 64), __shfl_xor(n.j, o, 64));
+      }
+      if (lane == 0) up = finish(v2, m, n, total) || up;
+    }
+  }
+  // (the loop's trip count is wave-uniform: the wave is whole here) one atomic per wave at most
+  if (__ballot(up) && lane == 0) atomicOr(flag, 1);
+}
+
+// Kernel 2: with the flag up EVERY cluster whose largest pair is void takes its non-void
+// candidate - those above one half included, as the reference's masked assignment does.
+__global__ __launch_bounds__(THREADS) void major_select_kernel(
+    const int32_t* __restrict__ flag, const int64_t* __restrict__ nv_obj,
+    const int64_t* __restrict__ nv_count, const int64_t* __restrict__ nv_y, int64_t G, int C,
+    int64_t* __restrict__ out_obj, int64_t* __restrict__ out_count, int64_t* __restrict__ out_y) {
+  if (!*flag) return;
+  const int64_t stride = (int64_t)gridDim.x * THREADS;
+  for (int64_t v = (int64_t)blockIdx.x * THREADS + threadIdx.x; v < G; v += stride) {
+    const int64_t l = out_y[v];
+    if (l < 0 || l >= C) {
+      out_obj[v] = nv_obj[v];
+      out_count[v] = nv_count[v];
+      out_y[v] = nv_y[v];
+    }
+  }
+}
+
+struct MajorPlan {
+  size_t off_flag, off_obj, off_count, off_y, total;
+};
+MajorPlan major_plan(int64_t G) {
+  MajorPlan m;
+  const size_t nb = align_up((size_t)(G > 0 ? G : 1) * 8, 256);
+  size_t off = 0;
+  m.off_flag = off; off += 256;
+  m.off_obj = off; off += nb;
+  m.off_count = off; off += nb;
+  m.off_y = off; off += nb;
+  m.total = off;
+  return m;
+}
+
 // ---- scratch of "sort n keys of key_bits bits, find the runs" ------------------------------------
 struct RunsPlan {
   size_t off_lo, off_order, off_hi, off_hig, off_perm, off_sort, off_scan, off_start, total;
@@ -798,6 +929,40 @@ extern "C" int spt_weighted_group_mean_f32(const float* x, int64_t n, int cols,
       ks, n, num_groups + 1, rowptr);
   weighted_mean_kernel<<<stream_grid(num_groups * cols, THREADS), THREADS, 0, stream>>>(
       x, w, n, cols, rowptr, order32, num_groups, out);
+  SPT_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" size_t spt_instance_major_workspace_bytes(int64_t G) {
+  if (!count_ok(G) || G < 1) return 0;
+  return major_plan(G).total;
+}
+
+extern "C" int spt_instance_major_i64(const int64_t* pointers, const int64_t* obj,
+                                      const int64_t* count, const int64_t* y, int64_t G, int64_t P,
+                                      int C, int64_t* out_obj, int64_t* out_count, int64_t* out_y,
+                                      int32_t* status, void* ws, size_t ws_bytes,
+                                      spt_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SPT_CHECK_ARG(count_ok(P) && P >= 1 && count_ok(G) && G >= 1, "P and G in 1 .. 2^31 - 2");
+  SPT_CHECK_ARG(C >= 1, "C >= 1");
+  SPT_CHECK_ARG(pointers && obj && count && y && out_obj && out_count && out_y && status,
+                "null pointer");
+  const MajorPlan m = major_plan(G);
+  SPT_CHECK_ARG(ws && ws_bytes >= m.total, "workspace too small");
+  char* base = (char*)ws;
+  int32_t* flag = (int32_t*)(base + m.off_flag);
+  SPT_CHECK_ARG(hipMemsetAsync(flag, 0, sizeof(int32_t), stream) == hipSuccess,
+                "could not queue the reset of the flag");
+  int64_t* nv_obj = (int64_t*)(base + m.off_obj);
+  int64_t* nv_count = (int64_t*)(base + m.off_count);
+  int64_t* nv_y = (int64_t*)(base + m.off_y);
+  const int g = stream_grid(G, THREADS);
+  major_candidates_kernel<<<g, THREADS, 0, stream>>>(pointers, obj, count, y, G, P, C, out_obj,
+                                                     out_count, out_y, nv_obj, nv_count, nv_y,
+                                                     flag, status);
+  major_select_kernel<<<g, THREADS, 0, stream>>>(flag, nv_obj, nv_count, nv_y, G, C, out_obj,
+                                                 out_count, out_y);
   SPT_CHECK_LAUNCH();
   return 0;
 }

@@ -312,7 +312,9 @@ class SPTTrainStep:
         captured.  The batch is static by construction: a new batch of the same caps must be
         COPIED into the captured tensors (``nag`` levels, ``labels``), host-side run tables are
         those of the captured batch.  Kernel timers are off in a captured step (no timing events
-        inside a capture).  Returns self."""
+        inside a capture).  The caller must not hold a tensor of an eager step that still carries
+        its ``grad_fn`` (a loss kept without ``.detach()``, a hooked model output): ``last_loss`` is
+        dropped here, what the caller keeps is out of reach (see the comment below).  Returns self."""
         from . import ops as _ops
         from . import csr as _csr_mod
         if self.graph is not None:
@@ -559,7 +561,16 @@ class SPTPanopticStep(SPTTrainStep):
     name = ("SuperCluster panoptic (spt-2 + edge-affinity head) fwd + CE/BCE loss + bwd + AdamW, "
             "incl. per-batch CSR builds")
 
-    def __init__(self, nag, dev, world=1, seed=0, model="spt64", kernel_timers=False):
+    def __init__(self, nag, dev, world=1, seed=0, model="spt64", kernel_timers=False,
+                 criterion=None, targets=None):
+        """``criterion`` + ``targets``: a ``criterion.PanopticCriterion`` and the batch's targets -
+        a mapping with ``y_hist`` (the label histograms of the output levels, finest first),
+        ``obj`` (the level-1 ``InstanceData``), ``obj_edge_affinity`` (f32, one per edge of the
+        trimmed level-1 graph) and optionally ``node_void`` (else ``predict.void_mask`` of the
+        level-1 histogram).  The step then trains with the reference's ``model_step`` loss
+        instead of the stand-in (plain CE on random labels + BCE on random 0 / 1 affinities).
+        The targets are prepared once, here (the major objects of the nodes; host reads allowed);
+        ``edge_stats`` (``metrics.BinaryEdgeStats``) takes the step's tp / fp / tn / fn."""
         self.nag, self.dev, self.world = _NagView(nag), dev, world
         self.n = nag.num_points
         self.net_name, self.workload, self.k_timers = "spt64-panoptic", None, None
@@ -587,18 +598,46 @@ class SPTPanopticStep(SPTTrainStep):
         if kernel_timers:
             ops.enable_timer(self.tname)
         self.last_loss = None
+        if (criterion is None) != (targets is None):
+            raise ValueError("pass a criterion together with the batch's targets")
+        self.criterion = criterion.to(dev) if criterion is not None else None
+        self.targets = self._prepare_targets(targets, ne) if targets is not None else None
 
-    def step(self):
+    def _prepare_targets(self, targets, num_edges):
+        from types import SimpleNamespace
+        from . import metrics, panoptic, predict
+        dev = self.dev
+        y_hist = [t.to(dev) for t in targets["y_hist"]]
+        obj = targets["obj"].to(dev)
+        affinity = targets["obj_edge_affinity"].to(dev).float().contiguous()
+        if obj.num_groups != self.n[1] or affinity.shape[0] != num_edges:
+            raise ValueError(f"targets for {obj.num_groups} nodes / {affinity.shape[0]} edges, the "
+                             f"batch has {self.n[1]} / {num_edges}")
+        node_void = targets.get("node_void")
+        node_void = predict.void_mask(y_hist[0]) if node_void is None else node_void.to(dev)
+        node_obj, _, node_y = panoptic.major_objects(obj, NUM_CLASSES)
+        panoptic.verify_major(block=True)
+        self.edge_stats = metrics.BinaryEdgeStats(dev)
+        return SimpleNamespace(y_hist=y_hist, obj_edge_affinity=affinity, node_void=node_void,
+                               node_obj=node_obj, node_y=node_y)
+
+    def _fwd_bwd(self):
+        """Forward + loss + backward; the inherited ``step()`` / ``capture()`` / replay run it."""
         self._forget_csr()
-        self._timed_steps += 1
         logits, aff = self.model(self.nag)
-        loss = sum(l * self.loss_fn(lg, y) for l, lg, y in zip(self.lambdas, logits, self.labels))
-        loss = loss + self.bce(aff, self.affinity)          # edge_affinity_loss_lambda: 1
+        if self.criterion is not None:
+            t = self.targets
+            loss, semantic, edge = self.criterion(
+                logits, t.y_hist, aff, t.obj_edge_affinity, self.nag.levels[1]["obj_edge_index"],
+                t.node_void, t.node_obj, t.node_y, stats=self.edge_stats.state)
+            # detached: a live autograd graph of an eager step sends the backward of a later
+            # capture to the stream its AccumulateGrad nodes were created on (see capture())
+            self.last_semantic_loss, self.last_edge_affinity_loss = semantic.detach(), edge.detach()
+        else:
+            loss = sum(l * self.loss_fn(lg, y) for l, lg, y in zip(self.lambdas, logits, self.labels))
+            loss = loss + self.bce(aff, self.affinity)          # edge_affinity_loss_lambda: 1
         self.bucket.zero()
         loss.backward()
-        self.bucket.reduce()
-        self.opt.step()
-        self.last_loss = loss
         return loss
 
 class ScatterChain:

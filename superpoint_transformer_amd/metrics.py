@@ -227,3 +227,54 @@ class PanopticQuality3D:
         m.pq_modified_per_class = pq_mod
         m.mean_precision, m.mean_recall = precision.nanmean(), recall.nanmean()
         return m
+
+
+class BinaryEdgeStats:
+    """The edge-affinity metrics the panoptic module logs every step (``BinaryAccuracy`` and
+    ``BinaryF1Score`` on the sanitized edge affinities, src/models/panoptic.py:844-850) from four
+    int64 counters on the device: ``state = [tp, fp, tn, fn]`` of ``logit > 0`` against
+    ``target > 0.5`` over the edges that do not join two void nodes.  ``ops.edge_affinity_loss``
+    (``stats=metric.state``) fills them from the pass that computes the loss; ``update`` does the
+    same without a loss.  Neither reads the device from the host; ``compute`` reads it once.
+
+    One corner differs from torchmetrics: it applies a sigmoid to its input only when some value
+    lies outside [0, 1], so a batch whose logits ALL lie in [0, 1] is thresholded at 0.5 there.
+    Here the logit is always thresholded at 0.
+
+    ``oa()`` and ``f1()`` are float64; 0 / 0 (no edge counted; no positive in prediction or
+    target) gives 0.0, as torchmetrics' safe division does."""
+
+    def __init__(self, device=None):
+        self.state = torch.zeros(4, dtype=torch.int64, device=device)
+
+    def to(self, device):
+        self.state = self.state.to(device)
+        return self
+
+    def reset(self):
+        self.state.zero_()
+
+    def update(self, logits, target, edge_index, node_void):
+        """Add the kept edges of one batch (no host read)."""
+        if self.state.device != logits.device:
+            self.to(logits.device)
+        n = node_void.shape[0]
+        zeros = torch.zeros(n, dtype=torch.int64, device=logits.device)
+        ops.edge_affinity_loss(logits.detach(), target, edge_index, node_void, zeros, zeros,
+                               stats=self.state)
+
+    __call__ = update
+
+    def compute(self):
+        """``(tp, fp, tn, fn)`` as Python integers: THE host read."""
+        return tuple(self.state.tolist())
+
+    def oa(self):
+        tp, fp, tn, fn = self.compute()
+        total = tp + fp + tn + fn
+        return float(tp + tn) / total if total else 0.0
+
+    def f1(self):
+        tp, fp, tn, fn = self.compute()
+        den = 2 * tp + fp + fn
+        return float(2 * tp) / den if den else 0.0

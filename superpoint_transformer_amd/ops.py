@@ -1556,6 +1556,162 @@ def histogram_confusion_matrix(pred, target, num_classes, out=None):
 
 
 # ---------------------------------------------------------------------------
+# Edge-affinity loss of the panoptic model (csrc/loss.hip): BCE with logits over the edges that do
+# not join two void nodes, weighted by the edge's case, and the binary counters of the same pass
+# ---------------------------------------------------------------------------
+class _EdgeAffinityLossTorch(torch.autograd.Function):
+    """The kernels' rules as a torch composition (CPU tensors): fixed output sizes only, the term
+    and the gradient in float64 like the kernels, one rounding to the logits' dtype each."""
+
+    @staticmethod
+    def forward(ctx, logits, target, edge_index, node_void, node_obj, node_y, cw, pw, stats, status):
+        n = node_void.shape[0]
+        i, j = edge_index[0], edge_index[1]
+        ok = (i >= 0) & (i < n) & (j >= 0) & (j < n)
+        ic, jc = i.clamp(0, n - 1), j.clamp(0, n - 1)
+        void = node_void.bool()
+        keep = ok & ~(void[ic] & void[jc])
+        kind = 2 * (node_y[ic] != node_y[jc]).long() + (node_obj[ic] != node_obj[jc]).long()
+        w = torch.ones(i.shape[0], dtype=torch.float64, device=logits.device) if cw is None \
+            else cw.double()[kind]
+        zero = torch.zeros((), dtype=torch.float64, device=logits.device)
+        x = torch.where(keep, logits.detach().double(), zero)
+        t = target.detach().double()
+        pwd = pw.double().reshape(()) if pw is not None else zero + 1
+        lw = 1 + (pwd - 1) * t
+        l = (1 - t) * x + lw * ((-x).clamp(min=0) + torch.log1p(torch.exp(-x.abs())))
+        num = torch.where(keep, w * l, zero).sum()
+        den = torch.where(keep, w, zero).sum()
+        if stats is not None:
+            pred, tgt = logits.detach() > 0, target.detach() > 0.5
+            stats += torch.stack([(keep & pred & tgt).sum(), (keep & pred & ~tgt).sum(),
+                                  (keep & ~pred & ~tgt).sum(), (keep & ~pred & tgt).sum()])
+        if status is not None:
+            status[0] += (~ok).sum().to(status.dtype)
+        ctx.save_for_backward(x, t, w, keep, lw, pwd, den)
+        ctx.meta = logits.dtype
+        return (num / den).to(logits.dtype)
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, t, w, keep, lw, pwd, den = ctx.saved_tensors
+        g = gout.detach().double() * w / den * (lw * torch.sigmoid(x) - pwd * t)
+        return (torch.where(keep, g, torch.zeros_like(g)).to(ctx.meta),) + (None,) * 9
+
+
+class _EdgeAffinityLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, edge_index, node_void, node_obj, node_y, cw, pw, stats, status):
+        _lib.require_cuda(logits, target, edge_index, node_void, node_obj, node_y, cw, pw, stats,
+                          status)
+        lg, tg = _f32c(logits), _f32c(target)
+        e, n = lg.shape[0], node_void.shape[0]
+        dev = lg.device
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        den = torch.empty(1, dtype=torch.float64, device=dev)
+        nbytes = _lib.lib.spt_edge_affinity_loss_workspace_bytes(e)
+        ws = _workspace(nbytes, dev)
+        with torch.cuda.device(dev):
+            st = _lib.lib.spt_edge_affinity_loss_fwd_f32(
+                _lib.ptr(lg), _lib.ptr(tg), _lib.ptr(edge_index), e, _lib.ptr(node_void),
+                _lib.ptr(node_obj), _lib.ptr(node_y), n, _lib.ptr(cw), _lib.ptr(pw),
+                _lib.ptr(loss), _lib.ptr(den), _lib.ptr(stats), _lib.ptr(status), _lib.ptr(ws),
+                nbytes, _lib.stream_ptr(dev))
+        _lib.check(st, "spt_edge_affinity_loss_fwd_f32")
+        ctx.save_for_backward(lg, tg, edge_index, node_void, node_obj, node_y, cw, pw, den)
+        ctx.meta = logits.dtype
+        return loss[0].to(logits.dtype)
+
+    @staticmethod
+    def backward(ctx, gout):
+        lg, tg, edge_index, node_void, node_obj, node_y, cw, pw, den = ctx.saved_tensors
+        e, n = lg.shape[0], node_void.shape[0]
+        dev = lg.device
+        g = gout.detach().float().reshape(1).contiguous()
+        glog = torch.empty_like(lg)
+        with torch.cuda.device(dev):
+            st = _lib.lib.spt_edge_affinity_loss_bwd_f32(
+                _lib.ptr(lg), _lib.ptr(tg), _lib.ptr(edge_index), e, _lib.ptr(node_void),
+                _lib.ptr(node_obj), _lib.ptr(node_y), n, _lib.ptr(cw), _lib.ptr(pw), _lib.ptr(g),
+                _lib.ptr(den), _lib.ptr(glog), _lib.stream_ptr(dev))
+        _lib.check(st, "spt_edge_affinity_loss_bwd_f32")
+        return (glog.to(ctx.meta),) + (None,) * 9
+
+
+def edge_affinity_loss(logits, target, edge_index, node_void, node_obj, node_y, case_weights=None,
+                       pos_weight=None, stats=None, status=None):
+    """The edge-affinity loss of ``PanopticSegmentationModule.model_step``
+    (src/models/panoptic.py:726-796) without compacting anything: BCE with logits of ``logits``
+    f32 ``[E]`` against ``target`` f32 ``[E]`` in [0, 1] over the edges ``edge_index`` int64
+    ``[2, E]`` that do not join two void nodes (``node_void`` bool ``[N]``:
+    ``predict.void_mask(y_hist)``), differentiable in ``logits``.
+
+    ``node_obj`` / ``node_y`` int64 ``[N]``: the nodes' major object and its label
+    (``panoptic.major_objects``).  ``case_weights``: 4 weights for ``[same-class same-obj,
+    same-class diff-obj, diff-class same-obj, diff-class diff-obj]`` - the loss is then
+    ``sum(w l) / sum(w)`` over the kept edges (``WeightedBCEWithLogitsLoss``); ``None``: their
+    mean (``BCEWithLogitsLoss``).  ``pos_weight``: a number or a 1-element tensor (read on the
+    device).  A list of weights is copied to the device on every call, which a graph capture
+    refuses: inside a captured step pass device tensors (``criterion.EdgeAffinityCriterion``
+    keeps both as buffers).  No kept edge gives NaN (the mean of an empty tensor) and an
+    all-zero gradient.
+
+    ``stats``: optional int64 ``[4]`` buffer; tp, fp, tn, fn of ``logits > 0`` against
+    ``target > 0.5`` over the kept edges are ADDED to it by the same pass.  ``status``: optional
+    int32 ``[1]`` buffer counting edges with an end outside ``[0, N)``, which are dropped.
+    CUDA tensors run on the HIP kernels with no host synchronisation (the call can be captured
+    into a graph) and bitwise reproducibly; CPU tensors take a torch composition of the same
+    rules."""
+    if logits.dim() != 1 or not logits.is_floating_point():
+        raise ValueError(f"logits must be a floating [E] tensor, got {tuple(logits.shape)}")
+    e = logits.shape[0]
+    if tuple(target.shape) != (e,) or not target.is_floating_point():
+        raise ValueError(f"target must be a floating [{e}] tensor, got {tuple(target.shape)}")
+    if tuple(edge_index.shape) != (2, e) or edge_index.is_floating_point():
+        raise ValueError(f"edge_index must be an integer [2, {e}] tensor, got {tuple(edge_index.shape)}")
+    if node_void.dim() != 1 or node_void.dtype not in (torch.bool, torch.uint8):
+        raise ValueError("node_void must be a bool or uint8 [N] tensor")
+    n = node_void.shape[0]
+    if tuple(node_obj.shape) != (n,) or tuple(node_y.shape) != (n,) \
+            or node_obj.is_floating_point() or node_y.is_floating_point():
+        raise ValueError(f"node_obj and node_y must be integer [{n}] tensors")
+    dev = logits.device
+    for name, t in (("target", target), ("edge_index", edge_index), ("node_void", node_void),
+                    ("node_obj", node_obj), ("node_y", node_y)):
+        if t.device != dev:
+            raise ValueError(f"{name} lives on {t.device}, the logits on {dev}")
+    cw = pw = None
+    if case_weights is not None:
+        cw = torch.as_tensor(case_weights, dtype=torch.float32, device=dev).contiguous()
+        if tuple(cw.shape) != (4,):
+            raise ValueError(f"case_weights must hold 4 values, got {tuple(cw.shape)}")
+    if pos_weight is not None:
+        if torch.is_tensor(pos_weight):
+            if pos_weight.numel() != 1:
+                raise ValueError("pos_weight must be a scalar (one weight for the one output)")
+            pw = pos_weight.detach().to(device=dev, dtype=torch.float32).reshape(1).contiguous()
+        else:
+            pw = torch.full((1,), float(pos_weight), dtype=torch.float32, device=dev)
+    if stats is not None and (stats.dtype != torch.int64 or tuple(stats.shape) != (4,)
+                              or not stats.is_contiguous() or stats.device != dev):
+        raise ValueError(f"stats must be a contiguous int64 [4] tensor on {dev}")
+    if status is not None and (status.dtype != torch.int32 or status.numel() < 1
+                               or not status.is_contiguous() or status.device != dev):
+        raise ValueError(f"status must be a contiguous int32 tensor on {dev}")
+    if e == 0:                                    # decided from the shape: the mean of nothing
+        return logits.sum() + float("nan")
+    if n == 0:
+        raise ValueError("edges over an empty node set")
+    ei = edge_index.detach().long().contiguous()
+    void = node_void.detach().contiguous()
+    obj, y = node_obj.detach().long().contiguous(), node_y.detach().long().contiguous()
+    if logits.is_cuda:
+        return _EdgeAffinityLoss.apply(logits, target.detach(), ei, void, obj, y, cw, pw, stats,
+                                       status)
+    return _EdgeAffinityLossTorch.apply(logits, target, ei, void, obj, y, cw, pw, stats, status)
+
+
+# ---------------------------------------------------------------------------
 # Fused MLP: [bias-free Linear -> GraphNorm -> LeakyReLU] x L  (src/nn/mlp.py:8-94)
 # ---------------------------------------------------------------------------
 _GPTR_ATTR = "_spt_graph_ranges"

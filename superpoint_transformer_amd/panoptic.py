@@ -8,7 +8,9 @@ prediction and a Panoptic Quality in the reference's ``validation_step`` / ``tes
                          ``remove_void(C)[0].iou_and_size()`` gives without compacting anything;
 ``panoptic_counts_``     the five ``[C]`` counters ``PanopticQuality3D.compute``
                          (src/metrics/panoptic.py:225-323) is made of, added into a device state;
-``weighted_group_mean``  ``scatter_mean_weighted`` (src/utils/scatter.py:17-38).
+``weighted_group_mean``  ``scatter_mean_weighted`` (src/utils/scatter.py:17-38);
+``major_objects``        ``InstanceData.major`` (src/data/instance.py:162-225), the target object
+                         of each cluster in the edge-affinity loss, without a host read.
 
 Integer results are exact; ``iou`` is one correctly rounded f32 division of the two converted
 integers, as torch divides int64 tensors; the weighted mean equals the reference's CPU result
@@ -28,7 +30,7 @@ from . import _lib
 from .instance import InstanceData, _consecutive
 
 __all__ = ["merge_instances", "pair_stats", "panoptic_counts_", "weighted_group_mean",
-           "semantic_score",
+           "semantic_score", "major_objects", "verify_major",
            "new_state", "state_views", "MAX_CLASSES", "SEQUENTIAL_ROWS", "STATUS_WORDS"]
 
 MAX_CLASSES = 32          # of the per-workgroup tables of panoptic_counts_ on the device
@@ -427,3 +429,137 @@ def weighted_group_mean(x, idx, w, num_groups, check=True):
         if bad:
             raise ValueError(f"weighted_group_mean: {bad} index entries outside [0, {g})")
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+_MAJOR_FAULTS = ("{n} cluster(s) without a pair (the reference indexes out of range there)",
+                 "{n} fault(s) of pointers (not a monotone 0 .. num_pairs sequence)")
+_MAJOR_PENDING = []       # deferred verdicts of major_objects(check=True): (event | None, status)
+
+
+def _raise_major(words):
+    msgs = [_MAJOR_FAULTS[k].format(n=n) for k, n in enumerate(words) if n]
+    if msgs:
+        raise ValueError("major_objects: " + "; ".join(msgs))
+
+
+def verify_major(block=False):
+    """Read the statuses of the ``major_objects(check=True)`` calls that have COMPLETED
+    (``block``: wait for all of them, those recorded inside a captured graph included) and raise
+    ``ValueError`` for the first that counted a fault.  Never waits on the device unless asked."""
+    keep, failed = [], None
+    for ev, status in _MAJOR_PENDING:
+        if ev is None and not block:
+            keep.append((ev, status))
+            continue
+        if ev is not None:
+            if block:
+                ev.synchronize()
+            if not ev.query():
+                keep.append((ev, status))
+                continue
+        words = status.tolist()
+        if any(words) and failed is None:
+            failed = words
+    _MAJOR_PENDING[:] = keep
+    if failed is not None:
+        _raise_major(failed)
+
+
+def _first_argmax(values, cl, g):
+    """Per cluster the lowest pair index holding the cluster's largest value (``g`` where the
+    cluster is empty), and that value."""
+    p = values.numel()
+    best = torch.full((g,), torch.iinfo(torch.int64).min, dtype=torch.int64)
+    best.scatter_reduce_(0, cl, values, "amax", include_self=True)
+    j = torch.arange(p)
+    hit = values == best[cl]
+    arg = torch.full((g,), p, dtype=torch.int64)
+    arg.scatter_reduce_(0, cl[hit], j[hit], "amin", include_self=True)
+    return arg, best
+
+
+def _major_torch(d, c):
+    g, p = d.num_groups, d.num_items
+    ptr = d.pointers
+    sizes = ptr[1:] - ptr[:-1]
+    bad_ptr = int(bool(ptr[0] != 0) or bool(ptr[-1] != p)) + int((sizes < 0).sum())
+    if bad_ptr:
+        _raise_major((0, bad_ptr))
+    cl = torch.arange(g).repeat_interleave(sizes)
+    void = (d.y < 0) | (d.y >= c)
+    arg, count = _first_argmax(d.count, cl, g)
+    arg_nv, count_nv = _first_argmax(d.count * ~void, cl, g)
+    empty = arg >= p
+    a, a_nv = arg.clamp(max=p - 1), arg_nv.clamp(max=p - 1)
+    obj, y = d.obj[a], d.y[a]
+    major_void = ((y < 0) | (y >= c)) & ~empty
+    total = torch.zeros(g, dtype=torch.int64).index_add_(0, cl, d.count)
+    above = (count / total) > 0.5                                   # int64 / int64: f32 division
+    flag = (major_void & ~above).any()
+    take = major_void & flag
+    obj = torch.where(take, d.obj[a_nv], obj)
+    count = torch.where(take, count_nv, count)
+    y = torch.where(take, d.y[a_nv], y)
+    fill = torch.tensor(-1)
+    obj, y = torch.where(empty, fill, obj), torch.where(empty, fill, y)
+    count = torch.where(empty, torch.tensor(0), count)
+    return obj, count, y, int(empty.sum())
+
+
+def major_objects(instance_data, num_classes, check=True, status=None):
+    """``instance_data.major(num_classes)``: ``(obj, count, y)``, each int64 ``[num_clusters]`` -
+    per cluster the pair of the largest ``count`` (ties: the first pair of the cluster).  A pair
+    is void with ``y < 0`` or ``y >= num_classes``.  As the reference BEHAVES: if any cluster
+    whose largest pair is void holds it with ``count / total <= 0.5`` (int64 operands, divided as
+    f32), every cluster whose largest pair is void - those above one half included - takes the
+    pair of the largest ``count * ~void`` instead (an all-void cluster: its first pair, count 0);
+    otherwise none does.  On the device the decision is a flag between two kernels: no host read.
+
+    A cluster without a pair makes the reference index out of range; here it gets ``obj = -1,
+    count = 0, y = -1`` and is counted in ``status`` (int32 ``[2]``, added to: empty clusters,
+    faults of ``pointers``; a fresh one when not given).  ``check=True`` defers the verdict as
+    the CSR checks do: the status is read - without waiting - by a later ``major_objects`` call
+    or by ``verify_major(block=True)``, which raise ``ValueError``; CPU tensors raise at once.
+    ``check=False`` reports nothing; every access stays in bounds either way."""
+    d, c = instance_data, int(num_classes)
+    if c < 1:
+        raise ValueError("num_classes must be positive")
+    if d.num_items == 0:
+        raise AssertionError("At least one group index is required.")
+    _check_data(d)
+    dev = d.device
+    if not d.pointers.is_cuda:
+        obj, count, y, empty = _major_torch(d, c)
+        if status is not None:
+            status[0] += empty
+        if check and empty:
+            _raise_major((empty, 0))
+        return obj, count, y
+    capturing = torch.cuda.is_current_stream_capturing()
+    if _MAJOR_PENDING and not capturing:
+        verify_major()
+    g, p = d.num_groups, d.num_items
+    if status is None:
+        status = torch.zeros(2, dtype=torch.int32, device=dev)
+    obj = torch.empty(g, dtype=torch.int64, device=dev)
+    count = torch.empty(g, dtype=torch.int64, device=dev)
+    y = torch.empty(g, dtype=torch.int64, device=dev)
+    L = _lib.lib
+    nbytes = L.spt_instance_major_workspace_bytes(g)
+    ws = _workspace(nbytes, dev)
+    with torch.cuda.device(dev):
+        st = L.spt_instance_major_i64(_lib.ptr(d.pointers), _lib.ptr(d.obj), _lib.ptr(d.count),
+                                      _lib.ptr(d.y), g, p, c, _lib.ptr(obj), _lib.ptr(count),
+                                      _lib.ptr(y), _lib.ptr(status), _lib.ptr(ws), nbytes,
+                                      _lib.stream_ptr(dev))
+    _lib.check(st, "spt_instance_major_i64")
+    if check and capturing:
+        _MAJOR_PENDING.append((None, status))                       # read on request only
+    elif check:
+        host = torch.empty(2, dtype=torch.int32).pin_memory()
+        host.copy_(status, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(dev))
+        _MAJOR_PENDING.append((ev, host))
+    return obj, count, y
