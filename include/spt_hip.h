@@ -27,6 +27,18 @@
  *   - row-major, contiguous tensors; f32 features; int64 indices as the
  *     reference hands them over (NAGCast, src/transforms/data.py:54-150);
  *     int32 perm/rowptr inside CSR views (N0 < 2^31 rows);
+ *   - base alignment: the kernels index rows from the base pointer and pick their vector width
+ *     from the row length alone, so a [rows, c] f32 tensor (input, gradient or output) whose rows
+ *     are whole 16-byte chunks (c % 4 == 0) must start on a 16-byte boundary (c % 2 == 0: 8 bytes;
+ *     else its elements' 4), and so must the int32 arg rows written next to it; int64 index
+ *     tensors are read one element at a time (8 bytes).  The segment (spt_segcsr_*,
+ *     spt_gather_rows_f32), GraphNorm (spt_graphnorm_fwd / stats / bwd / bwd_acc / apply /
+ *     bwd_stats), edge-affinity feature, unit-sphere assemble, attention (spt_edge_attn_*_ex_f32,
+ *     spt_attn_split_*: also the encoders' weights Wk / Wq / Wv), tall-skinny Linear (x, W, Wt, gy) and fused-layer entries (x, W, h, gy,
+ *     xprev, gx; the pool-fused pair also out, arg, argpos, raw; the fold's x0, W0, gW0) REFUSE a misaligned pointer with
+ *     the other argument checks, before anything is launched (status < 0, the argument named in
+ *     spt_last_error(), no output touched).  Memory from hipMalloc is 256-byte aligned; a view
+ *     into the middle of an allocation need not be (the Python wrappers copy such a view);
  *   - segment ops take a CSR view (perm, rowptr) of an UNSORTED index built by
  *     spt_csr_build(): rows of segment s are perm[rowptr[s] .. rowptr[s+1]) in
  *     ascending original order (stable), so reductions are deterministic and

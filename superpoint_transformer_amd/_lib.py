@@ -334,6 +334,28 @@ def ptr(t):
     return None if t is None else t.data_ptr()
 
 
+def dense(t, dtype=None, align=16):
+    """``t`` as the kernels' contract wants it (include/spt_hip.h: row-major, contiguous, of the
+    entry's element type, base address a multiple of ``align`` bytes), or None for None.
+
+    The SAME tensor object comes back when it already is all of that - the hot path hands over
+    fresh dense tensors and pays three attribute reads; anything else (a column slice, a strided
+    or transposed or expanded view, another dtype, a dense view that starts 4 or 8 bytes into a
+    16-byte line - a flat-buffer view, a row-narrowed view of rows that are no multiple of 16 bytes)
+    becomes one dense copy, which comes from the allocator and is therefore aligned.  Every
+    wrapper normalises its inputs and its incoming gradients through here: the kernels take raw
+    pointers and index them by shape alone."""
+    if t is None:
+        return None
+    if dtype is not None and t.dtype != dtype:
+        return t.to(dtype, memory_format=torch.contiguous_format)      # cast and layout in one copy
+    if not t.is_contiguous():
+        return t.contiguous()
+    if t.data_ptr() % align:
+        return t.clone()
+    return t
+
+
 def stream_ptr(device=None):
     """hipStream_t of torch's current stream, as an integer."""
     return torch.cuda.current_stream(device).cuda_stream

@@ -53,9 +53,7 @@ def build_csr(idx, num_seg):
     _lib.require_cuda(idx)
     if idx.dim() != 1:
         raise ValueError("segment index must be 1-D")
-    if idx.dtype != torch.int64:
-        idx = idx.long()
-    idx = idx.contiguous()
+    idx = _lib.dense(idx, torch.int64, 8)
     n = idx.numel()
     num_seg = int(num_seg)
     if num_seg < 1:
@@ -279,9 +277,7 @@ def adopt_csr(idx, num_seg, pointers, points, ascending=None, verify="now"):
     if bad == vkey:
         return None                     # this very pair failed the check before
     dev = idx.device
-    pl = points if points.dtype == torch.int64 else points.long()
-    ql = pointers if pointers.dtype == torch.int64 else pointers.long()
-    pl, ql = pl.contiguous(), ql.contiguous()
+    pl, ql = _lib.dense(points, torch.int64, 8), _lib.dense(pointers, torch.int64, 8)
     flag = torch.zeros(1, dtype=torch.int32, device=dev)
     perm = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
     rowptr = torch.empty(num_seg + 1, dtype=torch.int32, device=dev)
@@ -445,9 +441,7 @@ def edge_csr_of(edge_index, num_nodes):
     # plumbing: the targets in CSR order (one gather per batch and level)
     e = edge_index.shape[1]
     tgt_sorted = torch.empty(max(e, 1), dtype=torch.int32, device=edge_index.device)[:e]
-    tgt64 = edge_index[1].contiguous()
-    if tgt64.dtype != torch.int64:
-        tgt64 = tgt64.long()
+    tgt64 = _lib.dense(edge_index[1], torch.int64, 8)
     with torch.cuda.device(edge_index.device):
         st = _lib.lib.spt_csr_gather_i64_i32(_lib.ptr(tgt64), _lib.ptr(view.perm), e,
                                              _lib.ptr(tgt_sorted), _lib.stream_ptr(edge_index.device))

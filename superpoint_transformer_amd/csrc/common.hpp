@@ -31,6 +31,18 @@ int fail(int code, const char* fmt, ...);
                          hipGetErrorString(e__));                             \
   } while (0)
 
+// Base alignment of a caller's pointer.  The row kernels choose their vector width from the row
+// length alone (4 floats where it is a multiple of 4, else 2, else 1) and index the rows from the
+// base, so the base must be a multiple of `4 * vec` bytes: refused on the host, with the other
+// argument checks and ahead of the first launch.  NULL passes (a nullable argument is checked where
+// it is required).
+static inline bool aligned_to(const void* p, size_t bytes) {
+  return ((uintptr_t)p & (uintptr_t)(bytes - 1)) == 0;
+}
+#define SPT_CHECK_ALIGNED(p, bytes)                  \
+  SPT_CHECK_ARG(::spt::aligned_to((p), (bytes)),     \
+                #p " must be aligned to its rows' vector width (16 bytes for rows of 4 k floats)")
+
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
 

@@ -852,6 +852,14 @@ extern "C" int spt_edge_attn_fwd_ex_f32(const float* qkv, int64_t n, int H, int 
   SPT_CHECK_ARG(n >= 0 && e >= 0 && H >= 1 && D >= 1 && Dv >= 1, "bad shape");
   if (n == 0) return 0;
   SPT_CHECK_ARG(qkv && erowptr && out && (tgt_sorted || e == 0), "null pointer");
+  // rows of whole 16-byte chunks are read and written as such (every kernel family)
+  SPT_CHECK_ALIGNED(qkv, (2 * H * D + H * Dv) % 4 == 0 ? 16 : 4);
+  SPT_CHECK_ALIGNED(edge_attr, F % 4 == 0 ? 16 : 4);
+  SPT_CHECK_ALIGNED(out, (H * Dv) % 4 == 0 ? 16 : 4);
+  // (the matrix-pipe kernels read the encoders' weight rows as float4)
+  SPT_CHECK_ALIGNED(Wk, F % 4 == 0 ? 16 : 4);
+  SPT_CHECK_ALIGNED(Wq, F % 4 == 0 ? 16 : 4);
+  SPT_CHECK_ALIGNED(Wv, F % 4 == 0 ? 16 : 4);
   SPT_CHECK_ARG((m == nullptr) == (z == nullptr), "pass both m and z or neither");
   if (prec != 0 && attn_mfma_shape_ok(H, D, Dv, F, edge_attr && Wk && Wq && Wv)) {
     attn_fwd_mfma_launch(qkv, n, erowptr, eperm, tgt_sorted, edge_attr, Wk, bk, Wq, bq, Wv, bv,
@@ -1084,6 +1092,15 @@ extern "C" int spt_edge_attn_bwd_ex_f32(
   SPT_CHECK_ARG(n >= 0 && e >= 0 && H >= 1 && D >= 1 && Dv >= 1, "bad shape");
   if (n == 0) return 0;
   SPT_CHECK_ARG(qkv && erowptr && out && m && z && gout && gqkv && (tgt_sorted || e == 0), "null pointer");
+  SPT_CHECK_ALIGNED(qkv, (2 * H * D + H * Dv) % 4 == 0 ? 16 : 4);
+  SPT_CHECK_ALIGNED(gqkv, (2 * H * D + H * Dv) % 4 == 0 ? 16 : 4);
+  SPT_CHECK_ALIGNED(edge_attr, F % 4 == 0 ? 16 : 4);
+  SPT_CHECK_ALIGNED(gedge_attr, F % 4 == 0 ? 16 : 4);
+  SPT_CHECK_ALIGNED(out, (H * Dv) % 4 == 0 ? 16 : 4);
+  SPT_CHECK_ALIGNED(gout, (H * Dv) % 4 == 0 ? 16 : 4);
+  SPT_CHECK_ALIGNED(Wk, F % 4 == 0 ? 16 : 4);
+  SPT_CHECK_ALIGNED(Wq, F % 4 == 0 ? 16 : 4);
+  SPT_CHECK_ALIGNED(Wv, F % 4 == 0 ? 16 : 4);
   const bool has_rpe = edge_attr && (Wk || Wq || Wv);
   SPT_CHECK_ARG(!has_rpe || gedge_attr, "gedge_attr is required with RPE");
   if (!edge_attr) F = 32;

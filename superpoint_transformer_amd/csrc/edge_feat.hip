@@ -189,6 +189,8 @@ extern "C" int spt_edge_affinity_features_f32(const float* x, int64_t n, int C,
   SPT_CHECK_ARG(n >= 0 && e >= 0 && C >= 4 && C % 4 == 0, "bad shape (C must be a multiple of 4)");
   if (e == 0) return 0;
   SPT_CHECK_ARG(x && edge_a && edge_b && out, "null pointer");
+  SPT_CHECK_ALIGNED(x, 16);
+  SPT_CHECK_ALIGNED(out, 16);
   edge_affinity_fwd_kernel<<<stream_grid(e * (C / 4), 256), 256, 0, stream>>>(x, edge_a, edge_b, e,
                                                                              C, out);
   SPT_CHECK_LAUNCH();
@@ -203,6 +205,9 @@ extern "C" int spt_edge_affinity_features_bwd_f32(const float* x, const float* g
   SPT_CHECK_ARG(n >= 0 && e >= 0 && C >= 4 && C % 4 == 0, "bad shape (C must be a multiple of 4)");
   if (e == 0) return 0;
   SPT_CHECK_ARG(x && gout && edge_a && edge_b && gend, "null pointer");
+  SPT_CHECK_ALIGNED(x, 16);
+  SPT_CHECK_ALIGNED(gout, 16);
+  SPT_CHECK_ALIGNED(gend, 16);
   edge_affinity_bwd_kernel<<<stream_grid(e * (C / 4), 256), 256, 0, stream>>>(x, gout, edge_a, edge_b,
                                                                              e, C, gend);
   SPT_CHECK_LAUNCH();

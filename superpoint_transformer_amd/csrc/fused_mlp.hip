@@ -1982,6 +1982,10 @@ static int fmlp_fwd_impl(const char* fn, const float* x, const FmlpRuns& rt, int
   SPT_CHECK_ARG(K >= 1 && N >= 16, "bad shape");
   SPT_CHECK_ARG(spt_fused_linear_supported(K, N), "(K, N) not built");
   SPT_CHECK_ARG(x && W && h && (total || norm) && ws, "null pointer");
+  // tiles are staged with 16-byte loads where the rows are whole 16-byte chunks (stage_tile)
+  SPT_CHECK_ALIGNED(x, K % 4 == 0 ? 16 : 4);
+  SPT_CHECK_ALIGNED(W, K % 4 == 0 ? 16 : 4);
+  SPT_CHECK_ALIGNED(h, 16);
   SPT_CHECK_ARG(!norm || (norm->weight && norm->mean_scale && norm->mean && norm->rstd && norm->am &&
                           norm->scale), "incomplete norm tables");
   // the per-graph totals, or (norm) totals + the GraphNorm's forward tables, in one launch
@@ -2130,7 +2134,9 @@ static int fmlp_bwd_impl(bool pooled, const float* gy, const float* gout, const 
     SPT_CHECK_ARG(!pooled && !gx && fold_W0 && fold_gW0 && prev_norm && pre_am,
                   "fold: dense layer, no gx, norm tables");
     SPT_CHECK_ARG(spt_fused_linear_bwd_fold_supported(fold_K0, K, N, mode), "fold: shape pair or mode not built");
-    SPT_CHECK_ARG(((size_t)fold_x0 & (fold_K0 % 4 == 0 ? 15 : 3)) == 0, "fold: x0 alignment");
+    SPT_CHECK_ALIGNED(fold_x0, fold_K0 % 4 == 0 ? 16 : 4);
+    SPT_CHECK_ALIGNED(fold_W0, fold_K0 % 4 == 0 ? 16 : 4);
+    SPT_CHECK_ALIGNED(fold_gW0, fold_K0 % 4 == 0 ? 16 : 4);
   }
   // (prev_norm: the previous layer's backward tables are written by this call's post launch; its
   // statistics are then needed whether or not the caller wants the totals themselves)
@@ -2141,6 +2147,13 @@ static int fmlp_bwd_impl(bool pooled, const float* gy, const float* gout, const 
                 "incomplete norm tables");
   SPT_CHECK_ARG(K >= 1 && N >= 16, "bad shape");
   SPT_CHECK_ARG(h && am && scale && bias && c1 && c2 && c3 && xprev && W && gW && ws, "null pointer");
+  SPT_CHECK_ALIGNED(gy, 16);
+  SPT_CHECK_ALIGNED(gout, 16);
+  SPT_CHECK_ALIGNED(arg, 16);
+  SPT_CHECK_ALIGNED(h, 16);
+  SPT_CHECK_ALIGNED(xprev, K % 4 == 0 ? 16 : 4);
+  SPT_CHECK_ALIGNED(W, K % 4 == 0 ? 16 : 4);
+  SPT_CHECK_ALIGNED(gx, K % 4 == 0 ? 16 : 4);
   SPT_CHECK_ARG(ws_bytes >= spt_fused_linear_workspace_bytes(K, N), "workspace too small");
   if (pooled) {
     SPT_CHECK_ARG(spt_fused_linear_pooled_supported_ex(K, N, g_fmlp_mode),
@@ -2618,6 +2631,12 @@ extern "C" int spt_fused_linear_fwd_pool_runs_f32(
   SPT_CHECK_ARG(x && pos_seg && rowptr && W && gn_weight && gn_bias && gn_mean_scale && pre_am &&
                 pre_scale && pre_bias && out && argpos && raw && gram && mean && rstd && am && scale && ws,
                 "null pointer");
+  SPT_CHECK_ALIGNED(x, 16);
+  SPT_CHECK_ALIGNED(W, 16);
+  SPT_CHECK_ALIGNED(out, 16);
+  SPT_CHECK_ALIGNED(arg, 16);
+  SPT_CHECK_ALIGNED(argpos, 16);
+  SPT_CHECK_ALIGNED(raw, 16);
   SPT_CHECK_ARG(num_seg >= 0 && n_rows >= 0 && (num_graphs == 1 || seg_graph), "bad shape");
   SPT_CHECK_ARG(ws_bytes >= spt_fused_linear_pool_workspace_bytes(K, N), "workspace too small");
   // the runs are the graphs' CSR position ranges: contiguous, starting at 0, ending at n_rows
@@ -2662,6 +2681,12 @@ static int fpool_bwd_entry(
   SPT_CHECK_ARG(gout && raw && argpos && pos_seg && am && scale && bias && c1 && c2 && c3 && xprev &&
                 pre_am && pre_scale && pre_bias && W && gram && gm && gx && gW && (prev_total || prev_norm) && ws,
                 "null pointer");
+  SPT_CHECK_ALIGNED(gout, 16);
+  SPT_CHECK_ALIGNED(raw, 16);
+  SPT_CHECK_ALIGNED(argpos, 16);
+  SPT_CHECK_ALIGNED(xprev, 16);
+  SPT_CHECK_ALIGNED(W, 16);
+  SPT_CHECK_ALIGNED(gx, 16);
   SPT_CHECK_ARG(num_seg >= 0 && (num_graphs == 1 || seg_graph), "bad shape");
   SPT_CHECK_ARG(ws_bytes >= spt_fused_linear_pool_workspace_bytes(K, N), "workspace too small");
   float* gwp = (float*)ws;

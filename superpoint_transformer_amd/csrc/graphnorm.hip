@@ -624,6 +624,8 @@ extern "C" int spt_graphnorm_fwd_f32(const float* x, const int64_t* batch, int64
   SPT_CHECK_ARG(gn_plan(r, d, B, &p), "dim > 1024 unsupported");
   if (int e = gn_check(r, d, B, p, ws, ws_bytes)) return e;
   SPT_CHECK_ARG(weight && bias && mean_scale && mean && rstd && (r == 0 || (x && y)), "null pointer");
+  SPT_CHECK_ALIGNED(x, 4 * p.sh.vec);
+  SPT_CHECK_ALIGNED(y, 4 * p.sh.vec);
   char* base = (char*)ws;
   double* partial = (double*)(base + p.off_partial);
   double* total = (double*)(base + p.off_total);
@@ -662,6 +664,7 @@ extern "C" int spt_graphnorm_stats_f32(const float* x, const int64_t* batch, int
   SPT_CHECK_ARG(gn_plan(r, d, B, &p), "dim > 1024 unsupported");
   if (int e = gn_check(r, d, B, p, ws, ws_bytes)) return e;
   SPT_CHECK_ARG(weight && mean_scale && mean && rstd && am && scale && (r == 0 || x), "null pointer");
+  SPT_CHECK_ALIGNED(x, 4 * p.sh.vec);
   double* partial = (double*)((char*)ws + p.off_partial);
   launch_stats<false>(p, x, nullptr, batch, r, d, B, nullptr, nullptr, nullptr, 1.f, partial, stream);
   gn_finalize_fwd_kernel<<<dim3(B, (d + 15) / 16), 256, 0, stream>>>(partial, p.nblocks, B, d, weight, mean_scale, eps, mean, rstd, am, scale);
@@ -699,6 +702,10 @@ extern "C" int spt_graphnorm_bwd_acc_f32(const float* x, const float* gy,
   SPT_CHECK_ARG(gn_plan(r, d, B, &p), "dim > 1024 unsupported");
   if (int e = gn_check(r, d, B, p, ws, ws_bytes)) return e;
   SPT_CHECK_ARG(weight && bias && mean_scale && mean && rstd && gweight && gbias && gmean_scale && (r == 0 || (x && gy && gx)), "null pointer");
+  SPT_CHECK_ALIGNED(x, 4 * p.sh.vec);
+  SPT_CHECK_ALIGNED(gy, 4 * p.sh.vec);
+  SPT_CHECK_ALIGNED(gx_add, 4 * p.sh.vec);
+  SPT_CHECK_ALIGNED(gx, 4 * p.sh.vec);
   char* base = (char*)ws;
   double* partial = (double*)(base + p.off_partial);
   double* total = (double*)(base + p.off_total);
@@ -753,6 +760,8 @@ extern "C" int spt_graphnorm_apply_f32(const float* x, const int64_t* batch, int
   SPT_CHECK_ARG(gn_plan(r, d, num_graphs, &p), "dim > 1024 unsupported");
   if (r == 0) return 0;
   SPT_CHECK_ARG(x && y && am && scale && bias, "null pointer");
+  SPT_CHECK_ALIGNED(x, 4 * p.sh.vec);
+  SPT_CHECK_ALIGNED(y, 4 * p.sh.vec);
   if (p.sh.vec == 4)
     gn_apply_fwd_kernel<4><<<p.nblocks * 2, GN_THREADS, 0, stream>>>(x, batch, r, d, p.sh.lpr_log2, am, scale, bias, act_slope, y);
   else if (p.sh.vec == 2)
@@ -776,6 +785,8 @@ extern "C" int spt_graphnorm_bwd_stats_f32(const float* x, const float* gy, cons
   SPT_CHECK_ARG(gn_plan(r, d, B, &p), "dim > 1024 unsupported");
   if (int e = gn_check(r, d, B, p, ws, ws_bytes)) return e;
   SPT_CHECK_ARG(total && am && scale && bias && (r == 0 || (x && gy)), "null pointer");
+  SPT_CHECK_ALIGNED(x, 4 * p.sh.vec);
+  SPT_CHECK_ALIGNED(gy, 4 * p.sh.vec);
   double* partial = (double*)((char*)ws + p.off_partial);
   launch_stats<true>(p, x, gy, batch, r, d, B, am, scale, bias, act_slope, partial, stream);
   gn_reduce_partials_kernel<<<dim3(B, (p.row_len + 15) / 16), 256, 0, stream>>>(partial, p.nblocks, B, p.row_len, total);

@@ -865,8 +865,11 @@ extern "C" int spt_segcsr_reduce_f32(int op, const float* x, const int32_t* perm
   SPT_CHECK_ARG(op >= SPT_SUM && op <= SPT_MAX, "unknown op");
   SPT_CHECK_ARG(n >= 0 && num_seg >= 0 && c >= 1, "bad shape");
   SPT_CHECK_ARG(rowptr && out && (x || n == 0), "null pointer");
-  if (num_seg == 0) return 0;
   const RowShape rs = row_shape(c);
+  SPT_CHECK_ALIGNED(x, 4 * rs.vec);
+  SPT_CHECK_ALIGNED(out, 4 * rs.vec);
+  SPT_CHECK_ALIGNED(arg, 4 * rs.vec);
+  if (num_seg == 0) return 0;
   const int rpg_log2 = rows_in_flight_log2(n, num_seg, rs.lpr_log2);
   const bool want_arg = arg != nullptr;
   switch (op) {
@@ -918,6 +921,9 @@ extern "C" int spt_segcsr_max_affine_f32(const float* x, const int32_t* perm,
   hipStream_t stream = (hipStream_t)stream_;
   SPT_CHECK_ARG(n >= 0 && num_seg >= 0 && c >= 4 && (c & 3) == 0, "c must be a multiple of 4");
   SPT_CHECK_ARG(rowptr && out && arg && am && scale && bias && (x || n == 0), "null pointer");
+  SPT_CHECK_ALIGNED(x, 16);
+  SPT_CHECK_ALIGNED(out, 16);
+  SPT_CHECK_ALIGNED(arg, 16);
   if (num_seg == 0) return 0;
   const RowShape rs = row_shape(c);
   SPT_CHECK_ARG(rs.vec == 4, "unsupported row shape");
@@ -952,6 +958,9 @@ extern "C" int spt_segcsr_max_affine_bf16(const void* x_bf16, const int32_t* per
   SPT_CHECK_ARG(n >= 0 && num_seg >= 0, "bad shape");
   SPT_CHECK_ARG(spt_segcsr_max_affine_bf16_supported(c, n), "bf16 rows: c = 128 and n >= 65536 only");
   SPT_CHECK_ARG(rowptr && out && arg && am && scale && bias && x_bf16, "null pointer");
+  SPT_CHECK_ALIGNED(x_bf16, 16);
+  SPT_CHECK_ALIGNED(out, 16);
+  SPT_CHECK_ALIGNED(arg, 16);
   if (num_seg == 0) return 0;
   Affine af;
   af.am = am; af.sc = scale; af.bs = bias; af.seg_graph = seg_graph; af.slope = act_slope;
@@ -979,6 +988,10 @@ extern "C" int spt_segcsr_max_affine_raw_f32(const void* x, int x_is_bf16, const
   SPT_CHECK_ARG(n >= 0 && num_seg >= 0, "bad shape");
   SPT_CHECK_ARG(spt_segcsr_max_affine_raw_supported(c, n), "raw output: c = 128 and n >= 65536 only");
   SPT_CHECK_ARG(rowptr && out && arg && raw && am && scale && bias && x, "null pointer");
+  SPT_CHECK_ALIGNED(x, 16);
+  SPT_CHECK_ALIGNED(out, 16);
+  SPT_CHECK_ALIGNED(arg, 16);
+  SPT_CHECK_ALIGNED(raw, 16);
   if (num_seg == 0) return 0;
   Affine af;
   af.am = am; af.sc = scale; af.bs = bias; af.seg_graph = seg_graph; af.slope = act_slope;
@@ -1004,6 +1017,8 @@ extern "C" int spt_segcsr_reduce_bwd_f32(int op, const float* gout,
   if (n == 0) return 0;
   SPT_CHECK_ARG(gout && idx && gx, "null pointer");
   const RowShape rs = row_shape(c);
+  SPT_CHECK_ALIGNED(gout, 4 * rs.vec);
+  SPT_CHECK_ALIGNED(gx, 4 * rs.vec);
   // wide rows (>= one 128-B line) and every row owned by a segment: stream in
   // CSR order; narrow rows keep coalesced idx-ordered writes.
   if (perm && rowptr && c * 4 >= 128 && n / (num_seg > 0 ? num_seg : 1) >= 2) {
@@ -1039,6 +1054,8 @@ extern "C" int spt_gather_rows_f32(const float* x, const int64_t* idx, int64_t n
   if (n == 0) return 0;
   SPT_CHECK_ARG(x && idx && out, "null pointer");
   const RowShape rs = row_shape(c);
+  SPT_CHECK_ALIGNED(x, 4 * rs.vec);
+  SPT_CHECK_ALIGNED(out, 4 * rs.vec);
   launch_gather<0>(rs.vec, x, nullptr, idx, nullptr, n, c, rs.lpr_log2, out, stream);
   SPT_CHECK_LAUNCH();
   return 0;

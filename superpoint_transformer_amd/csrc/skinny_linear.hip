@@ -973,6 +973,8 @@ extern "C" int spt_skinny_dw_pre_m_f32(const float* gy, const float* x, int64_t 
   SPT_CHECK_ARG(rows >= 0, "bad shape");
   SPT_CHECK_ARG(spt_skinny_dw_supported(K, N), "(K, N) not built");
   SPT_CHECK_ARG(gw && (rows == 0 || (gy && x)), "null pointer");
+  SPT_CHECK_ALIGNED(gy, 16);
+  SPT_CHECK_ALIGNED(x, 16);
   SPT_CHECK_ARG(ws && ws_bytes >= spt_skinny_dw_workspace_bytes(K, N), "workspace too small");
   const bool pre = pre_am != nullptr;
   SPT_CHECK_ARG(!pre || (pre_scale && pre_bias && spt_skinny_pre_supported(K, N, num_graphs)),
@@ -1071,6 +1073,8 @@ static int skinny_linear_impl(const float* x, int64_t rows, int K, const float* 
   SPT_CHECK_ARG(spt_skinny_linear_supported(K, N), "(K, N) not built");
   if (rows == 0) return 0;
   SPT_CHECK_ARG(x && W && y, "null pointer");
+  SPT_CHECK_ALIGNED(x, 16);
+  SPT_CHECK_ALIGNED(W, 16);
   const bool pre = pre_am != nullptr, resid = residual != nullptr;
   SPT_CHECK_ARG(ldwt == 0 || (!pre && !resid && N > 16), "transposed weight: the plain product only");
   SPT_CHECK_ARG(!pre || (pre_scale && pre_bias && spt_skinny_pre_supported(K, N, num_graphs)),
@@ -1198,6 +1202,8 @@ extern "C" int spt_skinny_linear_bwd_m_f32(const float* gy, const float* x, cons
                 "(K, N) not built, the f32-exact mode or num_graphs * K too large");
   SPT_CHECK_ARG(!pre || (pre_scale && pre_bias), "pre-normalisation: incomplete tables");
   SPT_CHECK_ARG(gw && (rows == 0 || (gy && x && W && gx)), "null pointer");
+  SPT_CHECK_ALIGNED(gy, 16);
+  SPT_CHECK_ALIGNED(x, 16);
   SPT_CHECK_ARG(ws && ws_bytes >= spt_skinny_linear_bwd_workspace_bytes(K, N), "workspace too small");
   if (rows == 0) {
     hipMemsetAsync(gw, 0, (size_t)N * K * sizeof(float), stream);

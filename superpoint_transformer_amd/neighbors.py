@@ -120,8 +120,8 @@ def frnn_grid_points(query, search, K, r, squared=True, inclusive=False, cell_si
     64 neighbours per query; the rest comes from continuation searches ("the K' nearest strictly
     after the last one found", ``spt_grid_knn_after_f32``), 64 at a time."""
     _lib.require_cuda(query, search)
-    q = query.detach().float().contiguous()
-    s = q if search is query else search.detach().float().contiguous()
+    q = _lib.dense(query.detach(), torch.float32)
+    s = q if search is query else _lib.dense(search.detach(), torch.float32)
     nq, ns = q.shape[0], s.shape[0]
     K = int(K)
     dev = q.device
@@ -219,7 +219,7 @@ def knn_1_features(xyz, k, r_max=1, k_min=1, raw=False, squared=True, formulatio
     if k + 1 > 64:
         raise ValueError("knn_1_features: k + 1 <= 64 (call knn_1 and geometric_features for more)")
     _lib.require_cuda(xyz)
-    p = xyz.detach().float().contiguous()
+    p = _lib.dense(xyz.detach(), torch.float32)
     n = p.shape[0]
     dev = p.device
     K = k + 1
@@ -308,7 +308,7 @@ def neighbors_dense_to_csr(nn):
     _lib.require_cuda(nn)
     if nn.dim() != 2:
         raise ValueError("nn must be [N, k]")
-    t = nn.long().contiguous()
+    t = _lib.dense(nn, torch.int64, 8)
     n, k = t.shape
     dev = t.device
     ptr = torch.empty(n + 1, dtype=torch.long, device=dev)
@@ -347,7 +347,7 @@ def spatial_order(xyz, points_per_cell=32):
     """int32 permutation grouping the points by the cells of a uniform grid holding
     about ``points_per_cell`` points each (one host sync for the bounding box)."""
     _lib.require_cuda(xyz)
-    p = xyz.detach().float().contiguous()
+    p = _lib.dense(xyz.detach(), torch.float32)
     n = p.shape[0]
     box = _bbox(p)
     ext = float((box[3:6] - box[0:3]).max())
@@ -419,7 +419,7 @@ def geometric_features(xyz, nn, k_min=1, add_self_as_neighbor=True, raw=False, o
         return _geometric_features_optimal(xyz, nn, int(k_min), int(k_step), int(k_min_search),
                                            bool(add_self_as_neighbor), raw, order)
     _lib.require_cuda(xyz, nn)
-    p = xyz.detach().float().contiguous()
+    p = _lib.dense(xyz.detach(), torch.float32)
     if nn.dtype != torch.int64:
         nn = nn.long()
     # a column slice of a wider row-major table (knn_1's result) is read in place
@@ -433,7 +433,7 @@ def geometric_features(xyz, nn, k_min=1, add_self_as_neighbor=True, raw=False, o
     if order is False:
         order = None                        # visit the points as stored
     if order is not None:
-        order = order.to(torch.int32).contiguous()
+        order = _lib.dense(order, torch.int32, 4)
     feats = torch.empty((n, 11), dtype=torch.float32, device=p.device)
     with torch.cuda.device(p.device):
         st = _lib.lib.spt_point_geof_dense_ld_f32(
@@ -449,11 +449,11 @@ def geometric_features_csr(xyz, nn_val, nn_ptr, k_min=1, add_self=False, raw=Tru
     row per neighbourhood: ``nn_ptr`` may describe fewer groups than ``xyz`` has
     rows (the sampled points of each segment, transforms/graph.py:234-242)."""
     _lib.require_cuda(xyz, nn_val, nn_ptr)
-    p = xyz.detach().float().contiguous()
+    p = _lib.dense(xyz.detach(), torch.float32)
     n = nn_ptr.numel() - 1
     feats = torch.empty((n, 11), dtype=torch.float32, device=p.device)
-    val64 = nn_val.long().contiguous()       # named: a converted copy must outlive the launch
-    ptr64 = nn_ptr.long().contiguous()
+    val64 = _lib.dense(nn_val, torch.int64, 8)       # named: a converted copy must outlive the launch
+    ptr64 = _lib.dense(nn_ptr, torch.int64, 8)
     with torch.cuda.device(p.device):
         st = _lib.lib.spt_point_geof_csr_f32(
             _lib.ptr(p), n, _lib.ptr(val64), _lib.ptr(ptr64), int(add_self), int(k_min),

@@ -125,16 +125,13 @@ class _timed:
             self.rec.append((self.a, b))
 
 
+_dense = _lib.dense          # the one place a tensor's layout is turned into the kernels' contract
+
+
 def _as_rows(x):
     """[n, ...] -> contiguous, 16B-aligned f32 [n, c] plus the trailing shape."""
     tail = x.shape[1:]
-    x2 = x.reshape(x.shape[0], -1)
-    if x2.dtype != torch.float32:
-        x2 = x2.float()
-    x2 = x2.contiguous()
-    if x2.data_ptr() % 16:
-        x2 = x2.clone()
-    return x2, tail
+    return _dense(x.reshape(x.shape[0], -1), torch.float32), tail
 
 
 def _seg_reduce_fwd(x2, csr, op, want_arg):
@@ -207,9 +204,7 @@ class _GatherRows(torch.autograd.Function):
     def forward(ctx, x, idx, csr_holder):
         _lib.require_cuda(x, idx)
         x2, tail = _as_rows(x)
-        if idx.dtype != torch.int64:
-            idx = idx.long()
-        idx = idx.contiguous()
+        idx = _dense(idx, torch.int64, 8)
         ctx.idx, ctx.holder = idx, csr_holder
         ctx.num_src, ctx.tail, ctx.in_dtype = x2.shape[0], tail, x.dtype
         out = _gather_fwd(x2, idx)
@@ -248,8 +243,8 @@ class _EdgeAffinityFeatures(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, edge_index):
         _lib.require_cuda(x, edge_index)
-        xc = x.detach().float().contiguous()
-        ei = edge_index.long().contiguous()
+        xc = _dense(x.detach(), torch.float32)
+        ei = _dense(edge_index, torch.int64, 8)
         n, c = xc.shape
         e = ei.shape[1]
         out = torch.empty((e, 2 * c), dtype=torch.float32, device=xc.device)
@@ -267,7 +262,7 @@ class _EdgeAffinityFeatures(torch.autograd.Function):
         xc, ei = ctx.saved_tensors
         n, c = xc.shape
         e = ei.shape[1]
-        g = gout.float().contiguous()
+        g = _dense(gout, torch.float32)
         gend = torch.empty((2 * e, c), dtype=torch.float32, device=xc.device)
         with torch.cuda.device(xc.device):
             st = _lib.lib.spt_edge_affinity_features_bwd_f32(
@@ -291,7 +286,7 @@ def segment_sum_i64(x, index, num_seg=None):
     _lib.require_cuda(x)
     csr = csr_of(index, num_seg)
     tail = x.shape[1:]
-    x2 = x.reshape(x.shape[0], -1).long().contiguous()
+    x2 = _dense(x.reshape(x.shape[0], -1), torch.int64, 8)
     c = x2.shape[1]
     out = torch.empty((csr.num_seg, c), dtype=torch.int64, device=x.device)
     with torch.cuda.device(x.device):
@@ -307,10 +302,7 @@ def segment_sum_i64(x, index, num_seg=None):
 # ---------------------------------------------------------------------------
 def _usn_args(pos, idx, w, num_super):
     _lib.require_cuda(pos)
-    pos = pos.detach()
-    if pos.dtype != torch.float32:
-        pos = pos.float()
-    pos = pos.contiguous()
+    pos = _dense(pos.detach(), torch.float32)
     n = pos.shape[0]
     dev = pos.device
     if idx is None:
@@ -323,13 +315,11 @@ def _usn_args(pos, idx, w, num_super):
         num_seg, perm, rowptr, idx_t = csr.num_seg, csr.perm, csr.rowptr, csr.idx
     wf = wi = None
     if w is not None:
-        w = w.detach().contiguous()
-        if w.dtype == torch.int64:
-            wi = w
-        elif w.is_floating_point():
-            wf = w.float()
+        w = w.detach()
+        if w.is_floating_point():
+            wf = _dense(w, torch.float32)
         else:
-            wi = w.long()
+            wi = _dense(w, torch.int64, 8)
     return pos, n, dev, num_seg, perm, rowptr, idx_t, wf, wi
 
 
@@ -414,16 +404,11 @@ class _GraphNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, batch, num_graphs, weight, bias, mean_scale, eps, slope):
         _lib.require_cuda(x)
-        x2 = x.contiguous()
-        if x2.dtype != torch.float32:
-            x2 = x2.float()
+        x2 = _dense(x, torch.float32)
         r, d = x2.shape
         dev = x2.device
-        if batch is not None:
-            batch = batch.contiguous()
-            if batch.dtype != torch.int64:
-                batch = batch.long()
-        w, b, a = (t.detach().float().contiguous() for t in (weight, bias, mean_scale))
+        batch = _dense(batch, torch.int64, 8)
+        w, b, a = (_dense(t.detach(), torch.float32) for t in (weight, bias, mean_scale))
         y = torch.empty_like(x2)
         mean = torch.empty((num_graphs, d), dtype=torch.float32, device=dev)
         rstd = torch.empty((num_graphs, d), dtype=torch.float32, device=dev)
@@ -445,7 +430,7 @@ class _GraphNorm(torch.autograd.Function):
         num_graphs, slope, in_dtype = ctx.meta
         r, d = x2.shape
         dev = x2.device
-        gy = gy.contiguous().float()
+        gy = _dense(gy, torch.float32)
         gx = torch.empty_like(x2)
         gw = torch.empty(d, dtype=torch.float32, device=dev)
         gb = torch.empty(d, dtype=torch.float32, device=dev)
@@ -481,10 +466,7 @@ def graph_norm(x, batch, weight, bias, mean_scale, eps=1e-5, num_graphs=None,
 def _f32c(t):
     if t is None:
         return None
-    t = t.detach()
-    if t.dtype != torch.float32:
-        t = t.float()
-    return t.contiguous()
+    return _dense(t.detach(), torch.float32)
 
 
 _EA_SHARE = os.environ.get("SPT_EA_GRAD_SHARE", "1") != "0"
@@ -949,8 +931,7 @@ def _skinny_ok(x, weight):
 def _skinny_launch(x, weight, bias, mode=-1):
     """y = x W^T + b on the MFMA skinny-GEMM kernel (csrc/skinny_linear.hip); ``mode``: the matrix
     mode word of the call (``precision.skinny_mode()``; -1 = the library's default)."""
-    x = x.contiguous()
-    weight = weight.contiguous()
+    x, weight, bias = _dense(x), _dense(weight), _dense(bias)
     rows, k = x.shape
     n = weight.shape[0]
     y = torch.empty((rows, n), dtype=torch.float32, device=x.device)
@@ -970,8 +951,8 @@ def _input_grad(g, weight, mode=-1):
     if (g.is_cuda and g.dtype == torch.float32 and weight.dtype == torch.float32 and g.dim() == 2
             and g.shape[0] >= _SKINNY_MIN_ROWS and n_in % 4 == 0 and n_in >= 64
             and _lib.lib.spt_skinny_linear_supported(n_out, n_in)):
-        g = g.contiguous()
-        w = weight.detach().contiguous()
+        g = _dense(g)
+        w = _dense(weight.detach())
         rows = g.shape[0]
         y = torch.empty((rows, n_in), dtype=torch.float32, device=g.device)
         with torch.cuda.device(g.device):
@@ -992,8 +973,8 @@ def _dw_batched(g, x):
     main = nb * _DW_CHUNK
     gw = None
     if nb > 0:
-        gm = g[:main].view(nb, _DW_CHUNK, g.shape[1])
-        xm = x[:main].view(nb, _DW_CHUNK, x.shape[1])
+        gm = g[:main].reshape(nb, _DW_CHUNK, g.shape[1])
+        xm = x[:main].reshape(nb, _DW_CHUNK, x.shape[1])
         gw = torch.bmm(gm.transpose(1, 2), xm).sum(0)
     if main < n:
         tail = g[main:].t() @ x[main:]
@@ -1010,7 +991,7 @@ def _skinny_dw_ok(g, x):
 def _skinny_dw(g, x, want_bias=False, mode=-1):
     """dW = G^T X (and, from the same pass, db = column sums of G) on the MFMA kernel of
     csrc/skinny_linear.hip (per-wave partials, fixed-order sum)."""
-    g, x = g.contiguous(), x.detach().contiguous()
+    g, x = _dense(g), _dense(x.detach())
     rows, k = x.shape
     n = g.shape[1]
     gw = torch.empty((n, k), dtype=torch.float32, device=x.device)
@@ -1052,7 +1033,7 @@ def _skinny_bwd_ok(g, x, weight, num_graphs, mode):
 def _skinny_bwd(g, x, weight, want_bias, mode, pre=None):
     """(gx, gw, gb) of y = x W^T + b from one pass over (g, x); ``pre`` = (am, scale, bias, batch, B):
     x normalised on its way in (the folded pre-norm), gx then is the gradient of the normalised rows."""
-    g, x, w = g.contiguous(), x.detach().contiguous(), weight.detach().contiguous()
+    g, x, w = _dense(g), _dense(x.detach()), _dense(weight.detach())
     rows, k = x.shape
     n = g.shape[1]
     dev = x.device
@@ -1092,12 +1073,14 @@ class _TallLinear(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, weight = ctx.saved_tensors
-        g = g.contiguous()
+        # (dense operands on the library routes below the row floor too: a GEMM on a transposed
+        # or strided view takes another kernel and gives other bits than on its dense copy)
+        g, x, weight = _dense(g), _dense(x.detach()), _dense(weight.detach())
         if (x.is_cuda and x.dtype == torch.float32 and g.dtype == torch.float32
                 and weight.dtype == torch.float32 and x.shape[0] >= _SKINNY_MIN_ROWS
                 and _lib.lib.spt_narrow_linear_bwd_supported(x.shape[1], g.shape[1])):
             # narrow head: dX, dW and db from one pass over (x, g)
-            xc, wc = x.detach().contiguous(), weight.detach().contiguous()
+            xc, wc = x, weight
             rows, k = xc.shape
             n = g.shape[1]
             dev = xc.device
@@ -1152,16 +1135,16 @@ class _ResidualLinear(torch.autograd.Function):
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
         ctx.smode = _precision.skinny_mode()
-        xd, wd = x.detach().contiguous(), weight.detach().contiguous()
+        xd, wd = _dense(x.detach()), _dense(weight.detach())
+        bd = None if bias is None else _dense(bias.detach(), torch.float32)
+        res = _dense(residual.detach())          # (named: a copy must outlive the launch)
         rows, k = xd.shape
         n = wd.shape[0]
         y = torch.empty((rows, n), dtype=torch.float32, device=xd.device)
         with torch.cuda.device(xd.device):
             st = _lib.lib.spt_skinny_linear_pre_m_f32(
-                _lib.ptr(xd), rows, k, _lib.ptr(wd),
-                _lib.ptr(None if bias is None else bias.detach().contiguous()), n, _lib.ptr(y),
-                None, None, None, None, 1, _lib.ptr(residual.detach().contiguous()),
-                ctx.smode, _lib.stream_ptr(xd.device))
+                _lib.ptr(xd), rows, k, _lib.ptr(wd), _lib.ptr(bd), n, _lib.ptr(y),
+                None, None, None, None, 1, _lib.ptr(res), ctx.smode, _lib.stream_ptr(xd.device))
         _lib.check(st, "spt_skinny_linear_pre_m_f32")
         return y
 
@@ -1215,17 +1198,14 @@ class _NormLinear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, batch, num_graphs, gn_w, gn_b, gn_a, eps, weight, bias):
         _lib.require_cuda(x)
-        xd = x.detach().contiguous()
+        xd = _dense(x.detach())
         rows, d = xd.shape
         dev = xd.device
         B = int(num_graphs)
-        if batch is not None:
-            batch = batch.contiguous()
-            if batch.dtype != torch.int64:
-                batch = batch.long()
-        w, b, a = (t.detach().float().contiguous() for t in (gn_w, gn_b, gn_a))
-        wd = weight.detach().contiguous()
-        bd = None if bias is None else bias.detach().contiguous()
+        batch = _dense(batch, torch.int64, 8)
+        w, b, a = (_dense(t.detach(), torch.float32) for t in (gn_w, gn_b, gn_a))
+        wd = _dense(weight.detach())
+        bd = None if bias is None else _dense(bias.detach(), torch.float32)
         n = wd.shape[0]
         mean, rstd, am, sc = (torch.empty((B, d), dtype=torch.float32, device=dev) for _ in range(4))
         y = torch.empty((rows, n), dtype=torch.float32, device=dev)
@@ -1259,7 +1239,7 @@ class _NormLinear(torch.autograd.Function):
         rows, d = xd.shape
         n = wd.shape[0]
         dev = xd.device
-        gy = gy.contiguous()
+        gy = _dense(gy)
         if ctx.needs_input_grad[7] and _skinny_bwd_ok(gy, xd, wd, B, ctx.smode):
             # gradient wrt the normalised rows, weight / bias gradient against the rows normalised
             # on the fly: one pass over (gy, x)
@@ -1282,7 +1262,7 @@ class _NormLinear(torch.autograd.Function):
         gx = torch.empty_like(xd)
         g_w, g_b, g_a = (torch.empty(d, dtype=torch.float32, device=dev) for _ in range(3))
         if gres is not None:
-            gres = gres.contiguous()
+            gres = _dense(gres)
         ws = _workspace(_lib.lib.spt_graphnorm_workspace_bytes(rows, d, B), dev)
         with torch.cuda.device(dev):
             st = _lib.lib.spt_graphnorm_bwd_acc_f32(
@@ -1343,7 +1323,7 @@ class _CrossEntropy(torch.autograd.Function):
     def forward(ctx, logits, target, ignore_index):
         _lib.require_cuda(logits, target)
         lg = _f32c(logits)
-        tg = target.long().contiguous()
+        tg = _dense(target, torch.int64, 8)
         rows, c = lg.shape
         dev = lg.device
         lse = torch.empty(rows, dtype=torch.float32, device=dev)
@@ -1365,7 +1345,7 @@ class _CrossEntropy(torch.autograd.Function):
         ignore_index, dtype = ctx.meta
         rows, c = lg.shape
         dev = lg.device
-        g = gout.detach().float().reshape(1).contiguous()
+        g = _dense(gout.detach().reshape(1), torch.float32, 4)
         glog = torch.empty_like(lg)
         with torch.cuda.device(dev):
             st = _lib.lib.spt_cross_entropy_bwd_f32(
@@ -1441,7 +1421,7 @@ class _HistLoss(torch.autograd.Function):
     def forward(ctx, logits, target, weight, mode, ignore_index, confmat):
         _lib.require_cuda(logits, target, weight, confmat)
         lg = _f32c(logits)
-        tg = target.long().contiguous()
+        tg = _dense(target, torch.int64, 8)
         wt = _f32c(weight)
         rows, c = lg.shape
         ncols = tg.shape[1] if tg.dim() == 2 else 0
@@ -1466,7 +1446,7 @@ class _HistLoss(torch.autograd.Function):
         rows, c = lg.shape
         ncols = tg.shape[1] if tg.dim() == 2 else 0
         dev = lg.device
-        g = gout.detach().float().reshape(1).contiguous()
+        g = _dense(gout.detach().reshape(1), torch.float32, 4)
         glog = torch.empty_like(lg)
         with torch.cuda.device(dev):
             st = _lib.lib.spt_hist_loss_bwd_f32(
@@ -1538,7 +1518,7 @@ def histogram_confusion_matrix(pred, target, num_classes, out=None):
         return out
     if pred.is_cuda and c <= 32:
         _lib.require_cuda(target, out)
-        pr, tg = pred.contiguous(), target.long().contiguous()
+        pr, tg = _dense(pred, torch.int64, 8), _dense(target, torch.int64, 8)
         with torch.cuda.device(pred.device):
             st = _lib.lib.spt_confusion_matrix_i64(
                 _lib.ptr(pr), _lib.ptr(tg), rows, c, tg.shape[1] if tg.dim() == 2 else 0,
@@ -1627,7 +1607,7 @@ class _EdgeAffinityLoss(torch.autograd.Function):
         lg, tg, edge_index, node_void, node_obj, node_y, cw, pw, den = ctx.saved_tensors
         e, n = lg.shape[0], node_void.shape[0]
         dev = lg.device
-        g = gout.detach().float().reshape(1).contiguous()
+        g = _dense(gout.detach().reshape(1), torch.float32, 4)
         glog = torch.empty_like(lg)
         with torch.cuda.device(dev):
             st = _lib.lib.spt_edge_affinity_loss_bwd_f32(
@@ -1682,14 +1662,14 @@ def edge_affinity_loss(logits, target, edge_index, node_void, node_obj, node_y, 
             raise ValueError(f"{name} lives on {t.device}, the logits on {dev}")
     cw = pw = None
     if case_weights is not None:
-        cw = torch.as_tensor(case_weights, dtype=torch.float32, device=dev).contiguous()
+        cw = _dense(torch.as_tensor(case_weights, dtype=torch.float32, device=dev))
         if tuple(cw.shape) != (4,):
             raise ValueError(f"case_weights must hold 4 values, got {tuple(cw.shape)}")
     if pos_weight is not None:
         if torch.is_tensor(pos_weight):
             if pos_weight.numel() != 1:
                 raise ValueError("pos_weight must be a scalar (one weight for the one output)")
-            pw = pos_weight.detach().to(device=dev, dtype=torch.float32).reshape(1).contiguous()
+            pw = _dense(pos_weight.detach().to(device=dev, dtype=torch.float32).reshape(1))
         else:
             pw = torch.full((1,), float(pos_weight), dtype=torch.float32, device=dev)
     if stats is not None and (stats.dtype != torch.int64 or tuple(stats.shape) != (4,)
@@ -1702,9 +1682,9 @@ def edge_affinity_loss(logits, target, edge_index, node_void, node_obj, node_y, 
         return logits.sum() + float("nan")
     if n == 0:
         raise ValueError("edges over an empty node set")
-    ei = edge_index.detach().long().contiguous()
-    void = node_void.detach().contiguous()
-    obj, y = node_obj.detach().long().contiguous(), node_y.detach().long().contiguous()
+    ei = _dense(edge_index.detach(), torch.int64, 8)
+    void = _dense(node_void.detach(), None, 1)
+    obj, y = _dense(node_obj.detach(), torch.int64, 8), _dense(node_y.detach(), torch.int64, 8)
     if logits.is_cuda:
         return _EdgeAffinityLoss.apply(logits, target.detach(), ei, void, obj, y, cw, pw, stats,
                                        status)
@@ -1880,13 +1860,12 @@ def _fmlp_forward(x, batch, runs, eps_list, slope_list, params, apply_last=True,
     the last GraphNorm): with ``apply_last=False`` the last norm + activation are left to the
     consumer (the fused max-pool)."""
     L = len(eps_list)
-    Ws = [params[4 * i].detach().float().contiguous() for i in range(L)]
-    gnw = [params[4 * i + 1].detach().float().contiguous() for i in range(L)]
-    gnb = [params[4 * i + 2].detach().float().contiguous() for i in range(L)]
-    gms = [params[4 * i + 3].detach().float().contiguous() for i in range(L)]
-    x2 = x.detach().contiguous()
-    if x2.dtype != torch.float32:
-        x2 = x2.float()
+    Ws = [_dense(params[4 * i].detach(), torch.float32) for i in range(L)]
+    gnw = [_dense(params[4 * i + 1].detach(), torch.float32) for i in range(L)]
+    gnb = [_dense(params[4 * i + 2].detach(), torch.float32) for i in range(L)]
+    gms = [_dense(params[4 * i + 3].detach(), torch.float32) for i in range(L)]
+    x2 = _dense(x.detach(), torch.float32)
+    batch = _dense(batch, torch.int64, 8)        # (the run table came from the caller's tensor)
     R = x2.shape[0]
     dev = x2.device
     B = runs.B
@@ -1999,7 +1978,7 @@ def _fmlp_backward(saved, meta, gy, top_total=None, pooled=None, top_tabs=None):
     B = runs.B
     nr, c_r0, c_r1, c_g = runs.c_arrays()
     sp = _lib.stream_ptr(dev)
-    g_cur = gy.contiguous().float() if gy is not None else None
+    g_cur = _dense(gy, torch.float32)
     grads = [None] * (4 * L)
     gx0 = None
     with torch.cuda.device(dev):
@@ -2039,7 +2018,7 @@ def _fmlp_backward(saved, meta, gy, top_total=None, pooled=None, top_tabs=None):
             # the bottom layer rides along (see FOLD_BOTTOM): this layer's gx is then never formed
             fold = (l == 1 and FOLD_BOTTOM and FUSE_POST and not need_gx0 and not store16
                     and not (pooled is not None and l == L - 1)
-                    and x2.dtype == torch.float32 and x2.data_ptr() % 16 == 0
+                    and x2.dtype == torch.float32
                     and bool(_lib.lib.spt_fused_linear_bwd_fold_supported(
                         int(Ws[0].shape[1]), K, N, lmode)))
             want_gx = (l > 0 or need_gx0) and not fold
@@ -2228,8 +2207,8 @@ class _FusedMLPMaxPool(torch.autograd.Function):
         _, saved_sub, h_prev, (pam, psc, pbs) = _fmlp_forward(
             x, batch, runs, eps_list[:L - 1], slope_list[:L - 1], params[:4 * (L - 1)],
             apply_last=False, fmode=fmode, store16=store16)
-        W = params[4 * (L - 1)].detach().float().contiguous()
-        gnw, gnb, gms = (params[4 * (L - 1) + i].detach().float().contiguous() for i in (1, 2, 3))
+        W = _dense(params[4 * (L - 1)].detach(), torch.float32)
+        gnw, gnb, gms = (_dense(params[4 * (L - 1) + i].detach(), torch.float32) for i in (1, 2, 3))
         N, K = W.shape
         R = h_prev.shape[0]
         dev = h_prev.device
@@ -2285,7 +2264,7 @@ class _FusedMLPMaxPool(torch.autograd.Function):
         S = csr.num_seg
         nr, c_r0, c_r1, c_g = runs.c_arrays()
         sp = _lib.stream_ptr(dev)
-        gout = gout.contiguous().float()
+        gout = _dense(gout, torch.float32)
         with torch.cuda.device(dev):
             # statistics of the top GraphNorm's backward from the pool's sparse gradient
             total = torch.empty((B, 2 * N + 1), dtype=torch.float64, device=dev)
@@ -2356,7 +2335,7 @@ class _FusedMLPMaxPool(torch.autograd.Function):
         R, N = h_last.shape
         dev = h_last.device
         B = runs.B
-        gout = gout.contiguous().float()
+        gout = _dense(gout, torch.float32)
         # statistics of the top GraphNorm's backward from the pool's SPARSE gradient (one
         # non-zero per (segment, channel)) instead of a pass over the dense [R, N] tensors
         total = None
@@ -2432,7 +2411,7 @@ def fused_mlp_maxpool(x, batch, num_graphs, layers, index, num_seg, seg_graph=No
     if runs is None or (runs.B > 1 and seg_graph is None):
         return None
     csr = index if isinstance(index, SegmentCSR) else csr_of(index, num_seg)
-    sg = None if runs.B <= 1 else seg_graph.long().contiguous()
+    sg = None if runs.B <= 1 else _dense(seg_graph, torch.int64, 8)
     params = [t for l in layers for t in l[:4]]
     return _FusedMLPMaxPool.apply(x, batch, runs, [l[4] for l in layers],
                                   [l[5] for l in layers], csr, sg, *params)

@@ -43,7 +43,7 @@ def sparse_sample(idx, n_max=32, n_min=1, mask=None, return_pointers=False, seed
     if not 0 <= n_min <= n_max:
         raise ValueError("need 0 <= n_min <= n_max")
     dev = idx.device
-    idx = idx.long().contiguous()
+    idx = _lib.dense(idx, torch.int64, 8)
     n = idx.numel()
     if num_segments is None:
         num_segments = int(idx.max()) + 1 if n else 1
@@ -51,7 +51,7 @@ def sparse_sample(idx, n_max=32, n_min=1, mask=None, return_pointers=False, seed
     if mask is not None:
         mask = torch.as_tensor(mask, device=dev)
         if mask.dtype == torch.bool:
-            m8 = mask.to(torch.uint8).contiguous()
+            m8 = _lib.dense(mask, torch.uint8, 1)
         else:                                   # tensor_idx semantics: a list of positions
             m8 = torch.zeros(n, dtype=torch.uint8, device=dev)
             m8[mask.long()] = 1
@@ -77,7 +77,7 @@ def sparse_sample(idx, n_max=32, n_min=1, mask=None, return_pointers=False, seed
 def scatter_std(x, idx, num_segments=None):
     """``torch_scatter.scatter_std(x, idx, dim=0)`` (unbiased; graph.py:285)."""
     _lib.require_cuda(x, idx)
-    x2 = x.detach().float().contiguous()
+    x2 = _lib.dense(x.detach(), torch.float32)
     squeeze = x2.dim() == 1
     x2 = x2.view(x2.shape[0], -1)
     csr = csr_of(idx, num_segments)
@@ -99,7 +99,7 @@ def scatter_pca(x, idx, num_segments=None):
     if x.dim() != 2 or x.shape[1] != 3:
         raise NotImplementedError("scatter_pca is built for 3-D points (the only use in the reference)")
     csr = csr_of(idx, num_segments)
-    p = x.detach().float().contiguous()
+    p = _lib.dense(x.detach(), torch.float32)
     val = torch.empty((csr.num_seg, 3), dtype=torch.float32, device=p.device)
     vec = torch.empty((csr.num_seg, 3, 3), dtype=torch.float32, device=p.device)
     with torch.cuda.device(p.device):
@@ -114,7 +114,7 @@ def scatter_mean_orientation(orientation, idx, num_segments=None):
     """Mean orientation of the vectors of each segment, up to sign, expressed in the
     z+ half-space (scatter.py:249-300)."""
     _lib.require_cuda(orientation, idx)
-    o = orientation.detach().float().contiguous()
+    o = _lib.dense(orientation.detach(), torch.float32)
     if o.dim() != 2 or o.shape[1] != 3:
         raise ValueError("orientation must be [N, 3]")
     csr = csr_of(idx, num_segments)
