@@ -1708,6 +1708,51 @@ int spt_instance_major_i64(const int64_t* pointers, const int64_t* obj, const in
                            int64_t* out_count, int64_t* out_y, int32_t* status, void* ws,
                            size_t ws_bytes, spt_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Superedges: subedges and the 7 stored edge features           (csrc/superedge.hip)
+ * subedges (src/utils/graph.py:99-463) + _minimalistic_horizontal_edge_features
+ * (src/transforms/graph.py:950-1060), one workgroup per edge, nothing expanded in memory.
+ *
+ * pos f32 [num_points, 3]; (perm, rowptr) the int32 CSR view of the point -> segment index;
+ * edges int64, trimmed, row 0 at edges[0 .. E), row 1 at edges[edge_stride ..]; anchors int64
+ * [2, E] dense (spt_cluster_pair_anchors_f32).  num_points <= 2^31 - 1, E and num_segments
+ * below 2^31 - 1: refused otherwise.  Everything read from device memory (segment ids, row
+ * pointers, anchors, point ids, offsets) is compared with its bound before it addresses
+ * anything; an edge that fails a check gets count 0 and a zero row.
+ *
+ * spt_superedge_capacity: C, the most points a side of an edge may have in the workgroup
+ *   kernel.  Classes: 0 = both sides 1 .. 64 points (a wave per edge), 1 = both sides 1 .. C
+ *   (256 threads per edge, both sides in 32 KiB of LDS), 2 = everything else (the caller's
+ *   composition).
+ * spt_superedge_classify: order int32 [E] = the edge ids of class 0, then 1, then 2, each
+ *   ascending; counts int64 [3].  Three flag arrays through the device scan.
+ * spt_superedge_f32: the first num_small + num_medium entries of `order`.  switches: bit 0
+ *   halfspace_filter, 1 bbox_filter, 2 target_pc_flip, 3 source_pc_sort.  count int32 [E] =
+ *   st_k per edge.  count_only != 0 stops there (edge_attr, pairs, uid untouched).  Otherwise
+ *   edge_attr f32 [E, 7] = mean_off, std_off (clipped to [-2, 2]), mean_dist; with pair_offset
+ *   (uint32 [E + 1], spt_superedge_pair_offsets) the pairs of edge e go to pairs[0 / num_pairs +
+ *   pair_offset[e] + rank] and uid likewise; without it no pair is written anywhere.  f32
+ *   arithmetic in the order of graph.subedges, covariance and eigen-solve in f64; equal sort
+ *   keys keep CSR order; sums are fixed trees of f64 partials, so runs are bit-equal.
+ * spt_superedge_pair_offsets: offsets uint32 [E + 1] = exclusive scan of max(count, 0), total
+ *   in the last slot (the caller guarantees it is below 2^32).  ws: at least
+ *   spt_superedge_workspace_bytes(E), which covers classify too.
+ * ---------------------------------------------------------------------- */
+int spt_superedge_capacity(void);
+size_t spt_superedge_workspace_bytes(int64_t num_edges);
+int spt_superedge_classify(const int32_t* rowptr, int64_t num_segments, const int64_t* edges,
+                           int64_t num_edges, int64_t edge_stride, int32_t* order,
+                           int64_t* counts, void* ws, size_t ws_bytes, spt_stream_t stream);
+int spt_superedge_pair_offsets(const int32_t* count, int64_t num_edges, uint32_t* offsets,
+                               void* ws, size_t ws_bytes, spt_stream_t stream);
+int spt_superedge_f32(const float* pos, int64_t num_points, const int32_t* perm,
+                      const int32_t* rowptr, int64_t num_segments, const int64_t* edges,
+                      int64_t num_edges, int64_t edge_stride, const int64_t* anchors,
+                      const int32_t* order, int64_t num_small, int64_t num_medium, float ratio,
+                      int k_min, float margin, int switches, int count_only, float* edge_attr,
+                      int32_t* count, const uint32_t* pair_offset, int64_t* pairs, int64_t* uid,
+                      int64_t num_pairs, spt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -289,6 +289,12 @@ SIGNATURES = {
     "spt_edge_affinity_loss_fwd_f32": (_int, [_p, _p, _p, _i64, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _p,
                                               _p, _sz, _p]),
     "spt_edge_affinity_loss_bwd_f32": (_int, [_p, _p, _p, _i64, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _p]),
+    "spt_superedge_capacity": (_int, []),
+    "spt_superedge_workspace_bytes": (_sz, [_i64]),
+    "spt_superedge_classify": (_int, [_p, _i64, _p, _i64, _i64, _p, _p, _p, _sz, _p]),
+    "spt_superedge_pair_offsets": (_int, [_p, _i64, _p, _p, _sz, _p]),
+    "spt_superedge_f32": (_int, [_p, _i64, _p, _p, _i64, _p, _i64, _i64, _p, _p, _i64, _i64, _f32, _int,
+                                 _f32, _int, _int, _p, _p, _p, _p, _p, _i64, _p]),
 }
 
 

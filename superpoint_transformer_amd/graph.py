@@ -15,7 +15,8 @@ from .csr import csr_of
 from .ops import segment_reduce
 
 __all__ = ["to_trimmed", "edge_wise_points", "base_vectors_3d", "subedges",
-           "partition_adjacency", "PartitionGraph"]
+           "partition_adjacency", "PartitionGraph", "superedge_features", "superedge_capacity",
+           "minimalistic_edge_features", "connect_isolated"]
 
 
 def to_trimmed(edge_index):
@@ -59,8 +60,14 @@ def edge_wise_points(points, index, edge_index, num_segments=None):
     """For every edge, all points of its source segment and all points of its target segment
     (edge.py:22-77): ``((S_points, S_idx, S_uid), (T_points, T_idx, T_uid))``; edges are
     identified by their rank in (source, target) order."""
-    csr = csr_of(index, num_segments)
-    pointers, order = csr.rowptr.long(), csr.perm.long()
+    if index.is_cuda:
+        csr = csr_of(index, num_segments)
+        pointers, order = csr.rowptr.long(), csr.perm.long()
+    else:                                               # the same view, by a stable sort
+        num = int(index.max()) + 1 if num_segments is None else int(num_segments)
+        order = torch.argsort(index, stable=True)
+        pointers = torch.zeros(num + 1, dtype=torch.long)
+        pointers[1:] = torch.cumsum(torch.bincount(index, minlength=num), 0)
     size = pointers[1:] - pointers[:-1]
     n = max(int(edge_index.max()) + 1 if edge_index.numel() else 1, 1)
     uid = torch.unique(edge_index[0] * n + edge_index[1], sorted=True, return_inverse=True)[1]
@@ -93,9 +100,13 @@ def subedges(points, index, edge_index, ratio=0.2, k_min=20, cycles=3, pca_on_cp
     """graph.py:99-463.  Returns ``(edge_index [2,E] trimmed, ST_pairs [2,M], ST_uid [M])``:
     pair m joins point ``ST_pairs[0,m]`` of the source segment with ``ST_pairs[1,m]`` of the
     target segment of edge ``ST_uid[m]``.  ``chunk_size`` / ``pca_on_cpu`` are accepted and
-    ignored (nothing here needs chunking, the PCA is a kernel)."""
+    ignored (nothing here needs chunking, the PCA is a kernel).  CPU tensors take the same steps on
+    torch alone (``_subedges_torch``)."""
     from .neighbors import _pair_anchors
     from .segment import scatter_pca
+    if not points.is_cuda:
+        return _subedges_torch(points, index, edge_index, ratio, k_min, cycles, margin,
+                               halfspace_filter, bbox_filter, target_pc_flip, source_pc_sort)
     _lib.require_cuda(points, index, edge_index)
     points = points.detach().float().contiguous()
     index = index.long().contiguous()
@@ -184,6 +195,302 @@ def subedges(points, index, edge_index, ratio=0.2, k_min=20, cycles=3, pca_on_cp
     S_idx, S_uid = sort_along(S_pts, S_idx, S_uid, s_v)
     T_idx, T_uid = sort_along(T_pts, T_idx, T_uid, t_v)
     return edge_index, torch.vstack((S_idx, T_idx)), S_uid
+
+
+# ---------------------------------------------------------------------------
+# The same rules in plain torch: the route of CPU tensors
+# ---------------------------------------------------------------------------
+def _gsum(x, uid, num):
+    out = torch.zeros((num,) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
+    return out.index_add_(0, uid, x)
+
+
+def _gext(x, uid, num, red):
+    out = torch.zeros((num,) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
+    index = uid.view([-1] + [1] * (x.dim() - 1)).expand_as(x)
+    return out.scatter_reduce(0, index, x, red, include_self=False)
+
+
+def _gargmin(value, uid, num):
+    """Position of every group's first smallest value."""
+    vmin = _gext(value, uid, num, "amin")
+    where = torch.arange(value.numel(), device=value.device)
+    where = torch.where(value == vmin[uid], where, torch.full_like(where, value.numel()))
+    return _gext(where, uid, num, "amin")
+
+
+def _pair_anchors_torch(points, index, edge_index, cycles, num_segments):
+    """``scatter_nearest_neighbor`` (src/utils/scatter.py:128-238) as ``neighbors._pair_anchors``
+    runs it: start at the centroids, ``cycles`` rounds of nearest-in-target, nearest-in-source;
+    ties to the first point in ascending order."""
+    E = edge_index.shape[1]
+    cnt = torch.bincount(index, minlength=num_segments).clamp(min=1).view(-1, 1)
+    centroid = (_gsum(points.double(), index, num_segments) / cnt).to(points.dtype)
+    (S_pts, S_idx, S_uid), (T_pts, T_idx, T_uid) = edge_wise_points(points, index, edge_index,
+                                                                   num_segments)
+    sc = centroid[edge_index[0]]
+    si = ti = None
+    for _ in range(int(cycles)):
+        ti = T_idx[_gargmin((T_pts - sc[T_uid]).norm(dim=1), T_uid, E)]
+        tc = points[ti]
+        si = S_idx[_gargmin((S_pts - tc[S_uid]).norm(dim=1), S_uid, E)]
+        sc = points[si]
+    return torch.stack((si, ti))
+
+
+def _pca_first_component(P, uid, num):
+    """Last column of ``scatter_pca``'s eigenvectors: f64 population covariance, ``eigh``."""
+    x = P.double()
+    cnt = torch.bincount(uid, minlength=num).clamp(min=1).view(-1, 1).double()
+    mean = _gsum(x, uid, num) / cnt
+    d = x - mean[uid]
+    cov = _gsum(d.unsqueeze(2) * d.unsqueeze(1), uid, num) / cnt.view(-1, 1, 1)
+    return torch.linalg.eigh(cov)[1][:, :, -1].to(P.dtype)
+
+
+def _subedges_torch(points, index, edge_index, ratio=0.2, k_min=20, cycles=3, margin=0.2,
+                    halfspace_filter=True, bbox_filter=True, target_pc_flip=True,
+                    source_pc_sort=False, dtype=torch.float32):
+    """``subedges`` step by step on torch alone (any device; the route of CPU tensors)."""
+    points = points.detach().to(dtype).contiguous()
+    index = index.long().contiguous()
+    edge_index = to_trimmed(edge_index.long())
+    E = edge_index.shape[1]
+    if E == 0:
+        z = torch.empty(0, dtype=torch.long, device=points.device)
+        return edge_index, torch.stack([z, z]), z
+    num_segments = int(index.max()) + 1
+    anchors = _pair_anchors_torch(points, index, edge_index, cycles, num_segments)
+    s_anchor, t_anchor = points[anchors[0]], points[anchors[1]]
+    base = base_vectors_3d(t_anchor - s_anchor)
+    (S_pts, S_idx, S_uid), (T_pts, T_idx, T_uid) = edge_wise_points(points, index, edge_index,
+                                                                   num_segments)
+
+    def to_anchor_base(X, uid, anchor):
+        d, b = X - anchor[uid], base[uid]
+        return torch.stack([(d[:, 0] * b[:, k, 0] + d[:, 1] * b[:, k, 1]) + d[:, 2] * b[:, k, 2]
+                            for k in range(3)], dim=1)
+
+    S_pts = to_anchor_base(S_pts, S_uid, s_anchor)
+    T_pts = to_anchor_base(T_pts, T_uid, t_anchor)
+
+    def take(mask, P, I, U):
+        kept = _gsum(mask.long(), U, E)
+        keep = torch.where(mask | (kept == 0)[U])[0]
+        return P[keep], I[keep], U[keep]
+
+    if halfspace_filter:
+        S_pts, S_idx, S_uid = take(S_pts[:, 0] <= margin, S_pts, S_idx, S_uid)
+        T_pts, T_idx, T_uid = take(T_pts[:, 0] >= -margin, T_pts, T_idx, T_uid)
+    if bbox_filter:
+        st_min = torch.max(_gext(S_pts[:, 1:], S_uid, E, "amin"),
+                           _gext(T_pts[:, 1:], T_uid, E, "amin")).clamp(max=-margin)
+        st_max = torch.min(_gext(S_pts[:, 1:], S_uid, E, "amax"),
+                           _gext(T_pts[:, 1:], T_uid, E, "amax")).clamp(min=margin)
+
+        def in_bbox(P, U):
+            return (P[:, 1:] >= st_min[U]).all(dim=1) & (P[:, 1:] <= st_max[U]).all(dim=1)
+        S_pts, S_idx, S_uid = take(in_bbox(S_pts, S_uid), S_pts, S_idx, S_uid)
+        T_pts, T_idx, T_uid = take(in_bbox(T_pts, T_uid), T_pts, T_idx, T_uid)
+
+    p = _group_sort(S_pts[:, 0], S_uid, descending=True)
+    S_pts, S_idx, S_uid = S_pts[p], S_idx[p], S_uid[p]
+    p = _group_sort(T_pts[:, 0], T_uid, descending=False)
+    T_pts, T_idx, T_uid = T_pts[p], T_idx[p], T_uid[p]
+
+    s_size = torch.bincount(S_uid, minlength=E)
+    t_size = torch.bincount(T_uid, minlength=E)
+    s_k = (s_size * ratio).long().clamp(min=k_min).min(s_size)
+    t_k = (t_size * ratio).long().clamp(min=k_min).min(t_size)
+    st_k = torch.min(s_k, t_k)
+    sel = _arange_interleave(st_k, torch.cumsum(s_size, 0) - s_size)
+    S_pts, S_idx, S_uid = S_pts[sel], S_idx[sel], S_uid[sel]
+    sel = _arange_interleave(st_k, torch.cumsum(t_size, 0) - t_size)
+    T_pts, T_idx, T_uid = T_pts[sel], T_idx[sel], T_uid[sel]
+
+    s_v = _pca_first_component(S_pts, S_uid, E)
+    t_v = _pca_first_component(T_pts, T_uid, E)
+    kk = st_k.clamp(min=1).view(-1, 1)
+
+    def mean_of(P, U):
+        return (_gsum(P.double(), U, E) / kk).to(P.dtype)
+
+    if target_pc_flip and not source_pc_sort:
+        T_proj = (T_pts * t_v[T_uid]).sum(dim=1)
+        t_minp = T_pts[_gargmin(T_proj, T_uid, E)]
+        st_u = t_minp - mean_of(S_pts, S_uid)
+        st_u = st_u / st_u.norm(dim=1).view(-1, 1)
+        flip = (s_v * t_v).sum(dim=1) <= (s_v * st_u).sum(dim=1)
+        t_v = torch.where(flip.view(-1, 1), -t_v, t_v)
+    elif source_pc_sort:
+        t_v = s_v
+
+    def sort_along(P, I, U, v):
+        proj = ((P - mean_of(P, U)[U]) * v[U]).sum(dim=1)
+        q = _group_sort(proj, U, descending=False)
+        return I[q], U[q]
+
+    S_idx, S_uid = sort_along(S_pts, S_idx, S_uid, s_v)
+    T_idx, T_uid = sort_along(T_pts, T_idx, T_uid, t_v)
+    return edge_index, torch.vstack((S_idx, T_idx)), S_uid
+
+
+# ---------------------------------------------------------------------------
+# Superedges: subedges and the stored edge features in one kernel
+# ---------------------------------------------------------------------------
+def minimalistic_edge_features(pos, pairs, uid, num_edges):
+    """The 7 stored features of every edge from its point pairs
+    (``_minimalistic_horizontal_edge_features``, src/transforms/graph.py:950-1060):
+    ``mean_off`` [3], ``std_off`` [3] (unbiased ``scatter_std`` of the offsets in
+    ``base_vectors_3d(mean_off)``, clipped to [-2, 2]; one pair gives 0), ``mean_dist`` =
+    sqrt(mean(norm(offset))), in ``pos``'s dtype.  ``uid`` [M] names the edge of every pair.  On
+    the device the f32 group sums are the CSR kernels', so two runs are bit-equal."""
+    E = int(num_edges)
+    pairs, uid = pairs.long(), uid.long()
+    if pos.is_cuda and pos.dtype == torch.float32 and uid.numel():
+        def gsum(x):
+            return segment_reduce(x.contiguous(), uid, E, "sum")
+    else:
+        def gsum(x):
+            return _gsum(x, uid, E)
+    offset = pos[pairs[1]] - pos[pairs[0]]
+    cnt = torch.bincount(uid, minlength=E).clamp(min=1).to(pos.dtype).view(-1, 1)
+    mean_off = gsum(offset) / cnt
+    base = base_vectors_3d(mean_off)[uid]
+    uvw = torch.stack([(offset * base[:, k]).sum(dim=1) for k in range(3)], dim=1)
+    dev = uvw - (gsum(uvw) / cnt)[uid]
+    std_off = (gsum(dev * dev) / ((cnt - 1).clamp(min=1) + 1e-6)).sqrt().clip(-2, 2)
+    mean_dist = (gsum(offset.norm(dim=1).view(-1, 1)) / cnt).sqrt()
+    return torch.cat((mean_off, std_off, mean_dist), dim=1)
+
+
+def connect_isolated(edge_index, pos, k, batch=None, num_nodes=None):
+    """``Data.connect_isolated(k)`` for a graph without ``edge_attr`` (src/data/data.py:481-524):
+    every node no edge touches gets edges to its ``k`` nearest other nodes (within its cloud
+    when ``batch`` is given), appended to ``edge_index``."""
+    N = pos.shape[0] if num_nodes is None else int(num_nodes)
+    linked = torch.zeros(N, dtype=torch.bool, device=pos.device)
+    linked[edge_index.flatten()] = True
+    is_out = torch.where(~linked)[0]
+    if is_out.numel() == 0:
+        return edge_index
+    nb, _ = _isolated_edges(pos.detach().float().contiguous(), is_out, int(k), batch)
+    source, target = is_out.repeat_interleave(int(k)), nb.flatten()
+    found = target >= 0
+    return torch.cat((edge_index, torch.stack((source[found], target[found]))), dim=1)
+
+
+def superedge_capacity():
+    """Most points a side of an edge may have for the workgroup kernel (``C`` of DESIGN 7.21)."""
+    return int(_lib.lib.spt_superedge_capacity())
+
+
+def superedge_features(pos, index, edge_index, ratio=0.2, k_min=20, cycles=3, margin=0.2,
+                       halfspace_filter=True, bbox_filter=True, target_pc_flip=True,
+                       source_pc_sort=False, return_pairs=False, num_segments=None):
+    """``subedges`` and ``_minimalistic_horizontal_edge_features`` in one pass per edge
+    (``csrc/superedge.hip``): returns ``(edge_index [2, E] trimmed, edge_attr [E, 7])`` and, with
+    ``return_pairs``, ``(pairs [2, M], uid [M])`` as ``subedges`` gives them.
+
+    ``pos`` [N0, 3] level-0 points, ``index`` [N0] their segment, ``edge_index`` [2, *] edges
+    between segments (trimmed here).  Edges whose two segments hold at most 64 points take a wave
+    each, up to ``superedge_capacity()`` points a workgroup with both sides in LDS; an edge with a
+    larger side goes through ``subedges`` + ``minimalistic_edge_features`` and is merged back by
+    edge id.  Host reads: the three class counts, and the number of pairs when they are asked
+    for.  CPU tensors take the torch composition of the same rules."""
+    if not pos.is_cuda:
+        ei, pairs, uid = _subedges_torch(pos, index, edge_index, ratio, k_min, cycles, margin,
+                                         halfspace_filter, bbox_filter, target_pc_flip,
+                                         source_pc_sort)
+        attr = minimalistic_edge_features(pos.detach().float(), pairs, uid, ei.shape[1])
+        return (ei, attr, pairs, uid) if return_pairs else (ei, attr)
+    from .neighbors import _pair_anchors
+    from .ops import _workspace
+    _lib.require_cuda(pos, index, edge_index)
+    if pos.dim() != 2 or pos.shape[1] != 3:
+        raise ValueError("pos must be [N, 3]")
+    if pos.shape[0] > 2 ** 31 - 1:
+        raise ValueError("superedge_features indexes points with 32 bits: more than 2^31 - 1 points")
+    p = _lib.dense(pos.detach(), torch.float32)
+    index = _lib.dense(index, torch.int64, 8)
+    edge_index = to_trimmed(edge_index.long()).contiguous()
+    E = edge_index.shape[1]
+    dev = p.device
+    if E == 0:
+        z = torch.empty(0, dtype=torch.long, device=dev)
+        attr = torch.empty((0, 7), dtype=torch.float32, device=dev)
+        return (edge_index, attr, torch.stack([z, z]), z) if return_pairs else (edge_index, attr)
+    if num_segments is None:
+        num_segments = int(index.max()) + 1
+    kw = dict(ratio=ratio, k_min=k_min, cycles=cycles, margin=margin,
+              halfspace_filter=halfspace_filter, bbox_filter=bbox_filter,
+              target_pc_flip=target_pc_flip, source_pc_sort=source_pc_sort)
+    csr = csr_of(index, num_segments)
+    anchors, _ = _pair_anchors(p, index, edge_index, cycles, num_segments)
+    L = _lib.lib
+    stream = _lib.stream_ptr(dev)
+    nbytes = L.spt_superedge_workspace_bytes(E)
+
+    order = torch.empty(E, dtype=torch.int32, device=dev)
+    counts = torch.empty(3, dtype=torch.int64, device=dev)
+    ws = _workspace(nbytes, dev)
+    with torch.cuda.device(dev):
+        st = L.spt_superedge_classify(_lib.ptr(csr.rowptr), csr.num_seg, _lib.ptr(edge_index), E, E,
+                                      _lib.ptr(order), _lib.ptr(counts), _lib.ptr(ws), nbytes, stream)
+    _lib.check(st, "spt_superedge_classify")
+    n_small, n_medium, n_large = counts.tolist()                  # host sync: the class counts
+
+    edge_attr = torch.empty((E, 7), dtype=torch.float32, device=dev)
+    count = torch.empty(E, dtype=torch.int32, device=dev)
+    large = l_pairs = l_uid = l_count = None
+    if n_large:                                                   # a side above the capacity
+        large = order[n_small + n_medium:].long()
+        sub = edge_index[:, large]
+        if int(sub.max()) >= csr.num_seg or int(sub.min()) < 0:
+            raise ValueError(f"edge_index names segments outside [0, {csr.num_seg})")
+        _, l_pairs, l_uid = subedges(p, index, sub, **kw)
+        l_count = torch.bincount(l_uid, minlength=n_large)
+        edge_attr[large] = minimalistic_edge_features(p, l_pairs, l_uid, n_large)
+        count[large] = l_count.int()
+
+    switches = (1 if halfspace_filter else 0) | (2 if bbox_filter else 0) \
+        | (4 if target_pc_flip else 0) | (8 if source_pc_sort else 0)
+
+    def launch(count_only, offsets, pairs, uid, M):
+        with torch.cuda.device(dev):
+            st = L.spt_superedge_f32(_lib.ptr(p), p.shape[0], _lib.ptr(csr.perm), _lib.ptr(csr.rowptr),
+                                     csr.num_seg, _lib.ptr(edge_index), E, E, _lib.ptr(anchors),
+                                     _lib.ptr(order), n_small, n_medium, float(ratio), int(k_min),
+                                     float(margin), switches, int(count_only), _lib.ptr(edge_attr),
+                                     _lib.ptr(count), _lib.ptr(offsets), _lib.ptr(pairs),
+                                     _lib.ptr(uid), M, stream)
+        _lib.check(st, "spt_superedge_f32")
+
+    if not return_pairs:
+        launch(0, None, None, None, 0)
+        return edge_index, edge_attr
+    # the offsets must exist before a pair is written: a count-only launch (projection and filters
+    # alone), the device scan, then the full launch
+    launch(1, None, None, None, 0)
+    M = int(count.sum())                                          # host sync: the number of pairs
+    if M >= 2 ** 32:
+        raise ValueError("more than 2^32 - 1 subedge pairs: split the edge list")
+    offsets = torch.empty(E + 1, dtype=torch.int32, device=dev)   # uint32 words
+    ws = _workspace(nbytes, dev)
+    with torch.cuda.device(dev):
+        st = L.spt_superedge_pair_offsets(_lib.ptr(count), E, _lib.ptr(offsets), _lib.ptr(ws), nbytes,
+                                          stream)
+    _lib.check(st, "spt_superedge_pair_offsets")
+    pairs = torch.empty((2, M), dtype=torch.int64, device=dev)
+    uid = torch.empty(M, dtype=torch.int64, device=dev)
+    launch(0, offsets, pairs, uid, M)
+    if n_large and l_uid.numel():
+        first = (torch.cumsum(l_count, 0) - l_count)[l_uid]
+        at = (offsets[:E][large].long() & 0xFFFFFFFF)[l_uid] \
+            + torch.arange(l_uid.numel(), device=dev) - first
+        pairs[:, at] = l_pairs
+        uid[at] = large[l_uid]
+    return edge_index, edge_attr, pairs, uid
 
 
 # ---------------------------------------------------------------------------

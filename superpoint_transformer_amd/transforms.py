@@ -14,7 +14,8 @@ __all__ = ["horizontal_edge_features", "EDGE_FEATURE_COLUMNS", "NodeSize", "Samp
            "PointFeatures", "AddKeysTo", "NAGJitterKey", "RandomTiltAndRotate",
            "RandomAnisotropicScale", "RandomAxisFlip", "NAGDropoutColumns", "NAGDropoutRows",
            "NAGColorAutoContrast", "NAGColorDrop", "GeometricAugmentation", "FeatureAugmentation",
-           "ColorAugmentation", "GridSampling3D", "SaveNodeIndex", "NAGSaveNodeIndex", "DataTo"]
+           "ColorAugmentation", "GridSampling3D", "SaveNodeIndex", "NAGSaveNodeIndex", "DataTo",
+           "NAGRemoveKeys", "SegmentFeatures", "RadiusHorizontalGraph"]
 
 EDGE_FEATURE_COLUMNS = [
     "mean_off_x", "mean_off_y", "mean_off_z", "std_off_x", "std_off_y", "std_off_z",
@@ -403,6 +404,133 @@ class AddKeysTo:
         data.add_keys_to(keys=self.keys, to=self.to, strict=self.strict,
                          delete_after=self.delete_after)
         return data
+
+
+class NAGRemoveKeys:
+    """``NAGRemoveKeys`` (src/transforms/data.py:154-218): drops the attributes ``keys`` from the
+    levels ``level`` names (an int, 'all', 'i+', 'i-'); ``strict`` raises on a missing key."""
+
+    def __init__(self, level="all", keys=None, strict=False):
+        from .features import sanitize_keys
+        assert isinstance(level, (int, str))
+        self.level, self.keys, self.strict = level, sanitize_keys(keys, default=()), strict
+
+    def __call__(self, nag):
+        for data, keys in zip(nag, _per_level(self.level, (), self.keys, nag.num_levels)):
+            for k in keys:
+                if k not in data and self.strict:
+                    raise Exception(f"key: {k} is not within Data keys: {set(data.keys)}")
+            for k in keys:
+                data[k] = None
+        return nag
+
+
+class SegmentFeatures:
+    """``SegmentFeatures`` (src/transforms/graph.py:117-321): the handcrafted features of every
+    level above 0 from the level-0 points, written into the level's attributes under the
+    reference's names (``<key>``, ``mean_<key>``, ``std_<key>``) by ``segment.segment_features``.
+    ``strict`` raises when a ``mean_keys`` / ``std_keys`` entry is no level-0 attribute; otherwise
+    the entry is skipped.  The sample of ``n_min`` .. ``n_max`` points per segment is drawn from
+    torch's generator (``torch.manual_seed``)."""
+
+    def __init__(self, n_max=32, n_min=5, keys=None, mean_keys=None, std_keys=None, strict=True):
+        from .features import POINT_FEATURES, sanitize_keys
+        from .segment import SEGMENT_BASE_FEATURES
+        self.n_max, self.n_min = n_max, n_min
+        self.keys = sanitize_keys(keys, default=SEGMENT_BASE_FEATURES)
+        self.mean_keys = sanitize_keys(mean_keys, default=POINT_FEATURES)
+        self.std_keys = sanitize_keys(std_keys, default=POINT_FEATURES)
+        self.strict = strict
+
+    def __call__(self, nag):
+        from .segment import segment_features
+        atoms = nag[0]
+        for what, keys in (("mean", self.mean_keys), ("std", self.std_keys)):
+            for key in keys:
+                if atoms.get(key) is None and self.strict:
+                    raise ValueError(f"No point key `{key}` to build '{what}_{key} key'")
+        mean_keys = [k for k in self.mean_keys if atoms.get(k) is not None]
+        std_keys = [k for k in self.std_keys if atoms.get(k) is not None]
+        attrs = {k: atoms[k] for k in set(mean_keys) | set(std_keys)}
+        for i in range(1, nag.num_levels):
+            data = nag[i]
+            out = segment_features(atoms.pos, nag.get_super_index(i), data.num_nodes,
+                                   sub_size=nag.get_sub_size(i, low=0), n_max=self.n_max,
+                                   n_min=self.n_min, keys=self.keys, mean_keys=mean_keys,
+                                   std_keys=std_keys, point_attrs=attrs)
+            for k, v in out.items():
+                data[k] = v
+        return nag
+
+
+class RadiusHorizontalGraph:
+    """``RadiusHorizontalGraph`` (src/transforms/graph.py:594-947): for every level above 0 the
+    graph of segments with points ``gap`` or less apart (``cluster_radius_nn_graph`` with at most
+    ``k_max`` neighbours), every node without an edge linked to its ``k_min`` nearest nodes
+    (``graph.connect_isolated``), trimmed, with the 7 stored edge features in ``edge_attr``
+    (``graph.superedge_features`` on ``csrc/superedge.hip``: the anchors of a level's final edge
+    list are searched once, not per chunk).  ``k_min``, ``k_max``, ``gap``, ``se_ratio``, ``se_min``,
+    ``cycles`` and ``margin`` may be lists, one entry per level above 0.  ``pca_on_cpu``,
+    ``chunk_size`` and ``verbose`` are accepted and ignored.  ``keys`` must hold 'mean_off',
+    'std_off' and 'mean_dist': all three are stored, as in the reference."""
+
+    def __init__(self, k_min=1, k_max=100, gap=0, se_ratio=0.2, se_min=20, cycles=3,
+                 pca_on_cpu=False, margin=0.2, chunk_size=100000, halfspace_filter=True,
+                 bbox_filter=True, target_pc_flip=True, source_pc_sort=False, keys=None,
+                 verbose=False):
+        from .features import sanitize_keys
+        if isinstance(k_min, list):
+            assert all([k > 0 for k in k_min]), \
+                "k_min must be 1 or more, to avoid any unpleasant downstream " \
+                "issues where nodes have no edge"
+        else:
+            assert k_min > 0, \
+                "k_min must be 1 or more, to avoid any unpleasant downstream " \
+                "issues where nodes have no edge"
+        self.k_min, self.k_max, self.gap = k_min, k_max, gap
+        self.se_ratio, self.se_min, self.cycles, self.margin = se_ratio, se_min, cycles, margin
+        self.pca_on_cpu, self.chunk_size, self.verbose = pca_on_cpu, chunk_size, verbose
+        self.halfspace_filter, self.bbox_filter = halfspace_filter, bbox_filter
+        self.target_pc_flip, self.source_pc_sort = target_pc_flip, source_pc_sort
+        self.keys = sanitize_keys(keys, default=("mean_off", "std_off", "mean_dist"))
+
+    def __call__(self, nag):
+        from .graph import connect_isolated, superedge_features, to_trimmed
+        from .neighbors import cluster_radius_nn_graph
+        if not all(k in self.keys for k in ("mean_off", "std_off", "mean_dist")):
+            raise NotImplementedError(
+                "For now, 'mean_off', 'std_off' and 'mean_dist' must all be computed, since we "
+                "must store them all into 'edge_attr'.")
+        n = nag.num_levels - 1
+
+        def per_level(v):
+            return list(v) if isinstance(v, list) else [v] * n
+        params = zip(range(1, nag.num_levels), *(per_level(v) for v in (
+            self.k_min, self.k_max, self.gap, self.se_ratio, self.se_min, self.cycles, self.margin)))
+        for i, k_min, k_max, gap, ratio, se_min, cycles, margin in params:
+            data = nag[i]
+            num_nodes = data.num_nodes
+            data.edge_index = None
+            data.edge_attr = None
+            if num_nodes < 2:
+                raise ValueError(f"Input NAG only has 1 node at level={i}. Cannot compute "
+                                 f"radius-based horizontal graph.")
+            if data.edge_keys:
+                raise NotImplementedError(f"edge keys {data.edge_keys} are not carried through the "
+                                          "horizontal graph")
+            super_index = nag.get_super_index(i)
+            edge_index, _ = cluster_radius_nn_graph(
+                nag[0].pos, super_index, k_max=k_max, gap=gap, batch=data.batch, trim=True,
+                cycles=cycles, num_clusters=num_nodes)
+            edge_index = connect_isolated(edge_index, data.pos, k_min, batch=data.batch,
+                                          num_nodes=num_nodes)
+            edge_index = to_trimmed(edge_index)
+            data.edge_index, data.edge_attr = superedge_features(
+                nag[0].pos, super_index, edge_index, ratio=ratio, k_min=se_min, cycles=cycles,
+                margin=margin, halfspace_filter=self.halfspace_filter,
+                bbox_filter=self.bbox_filter, target_pc_flip=self.target_pc_flip,
+                source_pc_sort=self.source_pc_sort, num_segments=num_nodes)
+        return nag
 
 
 # ---------------------------------------------------------------------------
