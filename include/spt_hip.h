@@ -686,9 +686,30 @@ int spt_neighbors_dense_to_csr(const int64_t* nn, int64_t n, int k, int64_t* ptr
  *   n_samples = clamp(floor(n_max * tanh(size / n_max)), n_min, size)   (n_max > 0)
  *             = clamp(round(sqrt(size)), n_min, size)                   (n_max <= 0)
  * mask (nullable, 1 = keep): heuristic on the unmasked sizes, then clamped to the
- * number of kept elements (sparse.py:180-205).  seed: counter-based RNG, same seed
- * => same draw.  out_ptr [num_seg+1] int64 (out_ptr[num_seg] = number of samples,
- * never more than n), out_idx [n] int64 (only the first out_ptr[num_seg] are written).
+ * number of kept elements (sparse.py:180-205).  out_ptr [num_seg+1] int64
+ * (out_ptr[num_seg] = number of samples, never more than n), out_idx [n] int64 (only the
+ * first out_ptr[num_seg] are written).
+ *
+ * The draw is a function of (idx, mask, n_max, n_min, seed) alone, specified to the bit
+ * (rand32 = the splitmix64 finaliser of csrc/rng.hpp; restated on the host by
+ * tests/sampling_reference.py, which tests/test_sampling_gpu.py holds the output to):
+ *   key[i]    = rand32(seed, i)                                    i in [0, n)
+ *   order1    = stable argsort of key, ascending, unsigned         (the shuffle)
+ *   bucket[p] = idx[order1[p]]  if 0 <= idx < num_seg and (mask == NULL or mask[order1[p]])
+ *               else num_seg                                       (tail bucket, never drawn)
+ *   order2    = order1[stable argsort of bucket]
+ *   kept[s]   = population of bucket s
+ *   size[s]   = number of i with idx[i] == s (mask ignored) when a mask is given, else kept[s]
+ *   cnt[s]    = min(max(heuristic(size[s]), n_min), size[s], kept[s])
+ *   heuristic = floor(f32(n_max) * tanh_f32(f32(size) / f32(n_max)))          n_max > 0
+ *             = round_half_even(sqrt_f32(f32(size)))                          n_max <= 0
+ *               (tanh_f32 = the correctly rounded f32 value, which is what the reference's
+ *               host evaluation gives over the whole saturation band)
+ *   out_ptr   = exclusive cumsum of cnt, length num_seg + 1
+ *   out_idx[out_ptr[s] + j] = order2[first position of bucket s + j]          j < cnt[s]
+ * Rows whose idx lies outside [0, num_seg) are never drawn and never counted in size.
+ * Equal keys (certain from about 1e5 elements on) keep ascending position: both sorts are
+ * stable.
  * ---------------------------------------------------------------------- */
 size_t spt_sparse_sample_workspace_bytes(int64_t n, int64_t num_seg);
 int spt_sparse_sample(const int64_t* idx, int64_t n, int64_t num_seg, const uint8_t* mask,

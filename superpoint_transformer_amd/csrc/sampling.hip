@@ -15,9 +15,12 @@
 //   with a mask: sizes for the heuristic are the UNMASKED ones, then clamped to the
 //   number of kept elements (sparse.py:180-205).
 //
-// Which elements are drawn depends on the RNG, so parity with the reference is on
-// the counts / pointers (exact) and on the sampling contract (members of the right
-// segment, distinct, kept by the mask, uniform) - see tests/test_sampling_gpu.py.
+// Which elements the REFERENCE draws depends on its RNG, so parity with it is on the
+// counts / pointers (exact) and on the sampling contract (members of the right segment,
+// distinct, kept by the mask, uniform) - tests/test_segment_gpu.py.  The draw made HERE
+// is specified to the bit in include/spt_hip.h (counter-based keys, two stable sorts,
+// integer counts) and held bit for bit to its host restatement
+// (tests/sampling_reference.py) by tests/test_sampling_gpu.py.
 #include "radix_sort.hpp"
 #include "rng.hpp"   // rand32(seed, counter)
 
