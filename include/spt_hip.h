@@ -1774,6 +1774,68 @@ int spt_superedge_f32(const float* pos, int64_t num_points, const int32_t* perm,
                       int32_t* count, const uint32_t* pair_offset, int64_t* pairs, int64_t* uid,
                       int64_t num_pairs, spt_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Greedy contour-prior partition                                  (merge.hip)
+ * The merge rounds of GreedyContourPriorPartition (src/transforms/partition.py:383-653,
+ * src/utils/components.py:11-130; the reference's loop lives in torch_graph_components, so the
+ * rounds are this project's own: DESIGN 7.22).  Component state: size int64 [C], feat f64
+ * [C, d] = sum of s_i x_i, pos f64 [C, 3] = sum of s_i pos_i.  No float atomics anywhere:
+ * every output is bitwise reproducible.  Sums over more than 512 members are 64 strided partial
+ * sums combined by the xor tree 32, 16, .., 1; shorter ones run serially from the first member.
+ *
+ * spt_component_graph_f32: quotient of an edge list (rows at [0..E) and [edge_stride..), any
+ *   order, both directions, duplicates, self loops) under index [num_nodes] (nullable =
+ *   identity, then num_components == num_nodes): ends relabelled, ordered lo < hi, lo == hi
+ *   dropped, sorted by (lo, hi) with a stable radix sort, equal pairs merged with reduce
+ *   (0 add, 1 mean, 2 max, 3 min, 4 mul) in f32 in input order.  edge_attr nullable = ones.
+ *   out_edges rows at [0..) and [out_stride..), out_attr: room for E entries, the first
+ *   counts[0] are written.  counts int64 [2]: edges out, edges with an end out of range
+ *   (dropped).
+ * spt_merge_means_f64: mean [C, d] = feat / size.
+ * spt_merge_choose_f64: per edge (a, b, w) of a component graph, g = f32(s_a s_b / (s_a + s_b)
+ *   * |m_a - m_b|^2 - reg * w) in f64 (the squares summed from column 0), and best [C] uint64 =
+ *   min over the edges at the component of (orderable bits of g) << 32 | other end; all ones
+ *   where the component has no edge.  gain f32 [E] nullable.
+ * spt_merge_resolve: a is active iff it has an edge and (size < min_size, or not
+ *   merge_only_small and g < 0).  parent [C] = the choice of an active a, else a; of two active
+ *   components that chose each other the smaller is its own parent.  active: device int64 count.
+ * spt_merge_jump: out [C] = parent[parent[.]] (out != parent); changed (nullable) device int64,
+ *   set to 1 when an entry moved, else 0.
+ * spt_merge_accumulate_f64: label [num_old] in [0, num_new), every new id used.  Sizes, feature
+ *   rows and (pos nullable, with pos_out) position rows summed per new id over its members in
+ *   ascending old id.
+ * spt_edge_weights_f32: dist [E] = f32(sqrt(sum_c (rows[a, c] - rows[b, c])^2)) in f64 from
+ *   column 0, rows f32 [num_nodes, cols] with leading dimension ld; sum: device f64 sum of dist
+ *   in a fixed order; bad: device int64 count of edges with an end out of range (dist 0).
+ * ---------------------------------------------------------------------- */
+size_t spt_component_graph_workspace_bytes(int64_t num_edges);
+int spt_component_graph_f32(const int64_t* edge_index, int64_t num_edges, int64_t edge_stride,
+                            const float* edge_attr, const int64_t* index, int64_t num_nodes,
+                            int64_t num_components, int reduce, int64_t* out_edges,
+                            int64_t out_stride, float* out_attr, int64_t* counts, void* ws,
+                            size_t ws_bytes, spt_stream_t stream);
+int spt_merge_means_f64(const double* feat, const int64_t* size, int64_t num_components, int d,
+                        double* mean, spt_stream_t stream);
+int spt_merge_choose_f64(const double* mean, const int64_t* size, int64_t num_components, int d,
+                         const int64_t* edges, int64_t num_edges, int64_t edge_stride,
+                         const float* weights, double reg, uint64_t* best, float* gain,
+                         spt_stream_t stream);
+int spt_merge_resolve(const uint64_t* best, const int64_t* size, int64_t num_components,
+                      int64_t min_size, int merge_only_small, int64_t* parent, int64_t* active,
+                      spt_stream_t stream);
+int spt_merge_jump(const int64_t* parent, int64_t num_components, int64_t* out, int64_t* changed,
+                   spt_stream_t stream);
+size_t spt_merge_accumulate_workspace_bytes(int64_t num_old, int64_t num_new);
+int spt_merge_accumulate_f64(const int64_t* label, int64_t num_old, int64_t num_new,
+                             const int64_t* size, const double* feat, int d, const double* pos,
+                             int64_t* size_out, double* feat_out, double* pos_out, void* ws,
+                             size_t ws_bytes, spt_stream_t stream);
+size_t spt_edge_weights_workspace_bytes(int64_t num_edges);
+int spt_edge_weights_f32(const float* rows, int64_t num_nodes, int cols, int64_t ld,
+                         const int64_t* edge_index, int64_t num_edges, int64_t edge_stride,
+                         float* dist, double* sum, int64_t* bad, void* ws, size_t ws_bytes,
+                         spt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -295,6 +295,17 @@ SIGNATURES = {
     "spt_superedge_pair_offsets": (_int, [_p, _i64, _p, _p, _sz, _p]),
     "spt_superedge_f32": (_int, [_p, _i64, _p, _p, _i64, _p, _i64, _i64, _p, _p, _i64, _i64, _f32, _int,
                                  _f32, _int, _int, _p, _p, _p, _p, _p, _i64, _p]),
+    "spt_component_graph_workspace_bytes": (_sz, [_i64]),
+    "spt_component_graph_f32": (_int, [_p, _i64, _i64, _p, _p, _i64, _i64, _int, _p, _i64, _p, _p, _p,
+                                       _sz, _p]),
+    "spt_merge_means_f64": (_int, [_p, _p, _i64, _int, _p, _p]),
+    "spt_merge_choose_f64": (_int, [_p, _p, _i64, _int, _p, _i64, _i64, _p, _f64, _p, _p, _p]),
+    "spt_merge_resolve": (_int, [_p, _p, _i64, _i64, _int, _p, _p, _p]),
+    "spt_merge_jump": (_int, [_p, _i64, _p, _p, _p]),
+    "spt_merge_accumulate_workspace_bytes": (_sz, [_i64, _i64]),
+    "spt_merge_accumulate_f64": (_int, [_p, _i64, _i64, _p, _p, _int, _p, _p, _p, _p, _p, _sz, _p]),
+    "spt_edge_weights_workspace_bytes": (_sz, [_i64]),
+    "spt_edge_weights_f32": (_int, [_p, _i64, _int, _i64, _p, _i64, _i64, _p, _p, _p, _p, _sz, _p]),
 }
 
 

@@ -15,7 +15,8 @@ __all__ = ["horizontal_edge_features", "EDGE_FEATURE_COLUMNS", "NodeSize", "Samp
            "RandomAnisotropicScale", "RandomAxisFlip", "NAGDropoutColumns", "NAGDropoutRows",
            "NAGColorAutoContrast", "NAGColorDrop", "GeometricAugmentation", "FeatureAugmentation",
            "ColorAugmentation", "GridSampling3D", "SaveNodeIndex", "NAGSaveNodeIndex", "DataTo",
-           "NAGRemoveKeys", "SegmentFeatures", "RadiusHorizontalGraph"]
+           "NAGRemoveKeys", "SegmentFeatures", "RadiusHorizontalGraph",
+           "GreedyContourPriorPartition"]
 
 EDGE_FEATURE_COLUMNS = [
     "mean_off_x", "mean_off_y", "mean_off_z", "std_off_x", "std_off_y", "std_off_z",
@@ -531,6 +532,88 @@ class RadiusHorizontalGraph:
                 bbox_filter=self.bbox_filter, target_pc_flip=self.target_pc_flip,
                 source_pc_sort=self.source_pc_sort, num_segments=num_nodes)
         return nag
+
+
+class GreedyContourPriorPartition:
+    """``GreedyContourPriorPartition`` (src/transforms/partition.py:383-653): a hierarchical
+    partition by greedy merges on the contour-prior energy, one level per entry of ``min_size`` /
+    ``reg`` (a scalar is repeated), on ``partition.merge_components_by_contour_prior_on_data``
+    (``csrc/merge.hip`` for CUDA tensors).  Takes a ``Data`` with ``pos``, ``x``, ``edge_index``
+    and returns a ``NAG``: level ``l`` gains ``super_index``, level ``l + 1`` carries ``pos``,
+    ``node_size``, ``sub``, ``x``, ``edge_index``, ``edge_attr`` and the int64 sums of ``y`` /
+    ``semantic_pred`` histograms when present.  As in the reference every level recomputes
+    ``edge_attr`` from ``edge_weight_mode`` (so 'unit' resets merged weights to one) and
+    ``spatial_weight`` appends ``spatial_weight * pos`` to ``x`` at every level.  Weights are f32
+    (the reference's 'unit' mode makes int64 ones).  ``sharding`` and ``verbose`` are accepted
+    and ignored.  Refused: ``k > 0`` and the two 'affinity' weight modes."""
+
+    def __init__(self, reg, min_size, spatial_weight=None, edge_weight_mode='unit', d_0=None,
+                 edge_reduce='add', k=0, w_adjacency=0, max_iterations=-1, verbose=False,
+                 sharding=None):
+        from .partition import EDGE_WEIGHT_MODES, REDUCES, check_edge_weight_mode
+        self.spatial_weight, self.edge_weight_mode, self.d_0 = spatial_weight, edge_weight_mode, d_0
+        self.edge_reduce, self.k, self.w_adjacency = edge_reduce, k, w_adjacency
+        self.max_iterations, self.verbose, self.sharding = max_iterations, verbose, sharding
+        assert edge_weight_mode in EDGE_WEIGHT_MODES, \
+            (f"Invalid edge weight mode: {edge_weight_mode}.\n"
+             f"Valid options are: {list(EDGE_WEIGHT_MODES)}")
+        check_edge_weight_mode(edge_weight_mode)
+        if k > 0:
+            raise NotImplementedError(
+                "k > 0 (reconnecting isolated components every round) is not built")
+        if edge_reduce not in REDUCES:
+            raise ValueError(f"edge_reduce must be one of {sorted(REDUCES)}, got {edge_reduce!r}")
+
+        def is_list(v):
+            return isinstance(v, (list, tuple))
+        if is_list(min_size):
+            num_levels = len(min_size)
+        elif is_list(reg):
+            num_levels = len(reg)
+        else:
+            num_levels = 1
+        assert isinstance(reg, (int, float)) or is_list(reg), \
+            "`reg` parameter expected a scalar or a List"
+        self.reg = list(reg) if is_list(reg) else [reg] * num_levels
+        assert isinstance(min_size, int) or is_list(min_size), \
+            "`min_size` parameter expected an int or a List"
+        self.min_size = list(min_size) if is_list(min_size) else [min_size] * num_levels
+        assert len(self.reg) == len(self.min_size), \
+            "Expected the same number of `reg` and `min_size` parameters"
+
+    def __call__(self, data):
+        from .data import Data, NAG
+        from .partition import edge_weights, merge_components_by_contour_prior_on_data
+        data_list = [data]
+        for level, (reg, min_size) in enumerate(zip(self.reg, self.min_size)):
+            d1 = data_list[level]
+            if d1.x is None or d1.pos is None or d1.edge_index is None:
+                raise ValueError("GreedyContourPriorPartition needs data.x, data.pos and data.edge_index")
+            d1.edge_attr = edge_weights(d1.pos, d1.x, d1.edge_index, self.edge_weight_mode, self.d_0)
+            if self.spatial_weight is not None and self.spatial_weight != 0:
+                x = d1.x if d1.x.dim() > 1 else d1.x.view(-1, 1)
+                d1.x = torch.cat([x, d1.pos * self.spatial_weight], dim=1)
+            d1, (X_merged, S_merged, E_cp, W_cp, P_merged, sub) = \
+                merge_components_by_contour_prior_on_data(
+                    d1, reg, min_size, False, self.k, self.w_adjacency, self.max_iterations,
+                    self.sharding, self.edge_reduce, self.verbose)
+            data_list[level] = d1
+            d2 = Data(pos=P_merged, node_size=S_merged, sub=sub, x=X_merged, edge_index=E_cp,
+                      edge_attr=W_cp)
+            for key in ('y', 'semantic_pred'):
+                if key not in d1:
+                    continue
+                hist = d1[key]
+                assert hist.dim() == 2, \
+                    f"Expected Data.{key} to hold `(num_nodes, num_classes)` histograms, not single labels"
+                if hist.is_cuda:
+                    from .ops import segment_sum_i64
+                    d2[key] = segment_sum_i64(hist.long(), d1.super_index, S_merged.numel())
+                else:
+                    d2[key] = torch.zeros((S_merged.numel(), hist.shape[1]), dtype=torch.int64) \
+                        .index_add_(0, d1.super_index, hist.long())
+            data_list.append(d2)
+        return NAG(data_list)
 
 
 # ---------------------------------------------------------------------------
