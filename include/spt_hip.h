@@ -1836,6 +1836,62 @@ int spt_edge_weights_f32(const float* rows, int64_t num_nodes, int cols, int64_t
                          float* dist, double* sum, int64_t* bad, void* ws, size_t ws_bytes,
                          spt_stream_t stream);
 
+/* ----------------------------------------------------------------------
+ * Stride-1 sparse 3D convolution (csrc/sparse_conv.hip).
+ *   out[i] = bias + sum over o ascending of x[j(i, o)] W[o],  W [K^3, c_in, c_out] row-major,
+ *   o = ((dz + r) K + (dy + r)) K + (dx + r), j(i, o) the voxel of i's batch item at
+ *   coords[i] + d (dx, dy, dz).  coords int32 [n, 3] (x, y, z), batch int64 [n] nullable.
+ *
+ * spt_sparse_bounds_i32: record int64 [8] = min, max of x, y, z, batch (0, 0 without a batch).
+ * Key layout (host arrays): origin[4] = the minimum of x, y, z MINUS r d, and of batch; bits[4]
+ *   = the width of (max - min + 2 r d) for x, y, z and of (max - min) for batch; 1 .. 63 bits in
+ *   all.  The padding is what keeps a neighbour position outside the bounds from meeting another
+ *   voxel's key; a layout that does not cover the data gives a wrong map, never a stray access.
+ * spt_sparse_map_count: sorts the keys, leaves skeys [n] / sorder [n] (sorted keys and the voxel
+ *   of each), rowptr [n + 1] (exclusive scan of the pairs per voxel), record int64 [2] = number
+ *   of pairs (64-bit: check it before rowptr is trusted), number of duplicate (batch, coords).
+ * spt_sparse_map_fill: the pairs of voxel i at [rowptr[i], rowptr[i + 1]), offsets ascending:
+ *   nbr (the neighbour j), off (the offset index o), row (i); num_pairs = rowptr[n].
+ * spt_sparse_map_by_offset: perm [P] = the pairs stably sorted by offset, optr [k3 + 1] the run
+ *   of each offset (for dW).
+ * spt_sparse_conv_fwd_f32: c_in, c_out 1 .. 64 (the Python route hands it c_out % 16 == 0, which
+ *   spt_sparse_conv_supported answers; the dX call hands it the transposed shape).  flip != 0
+ *   reads W[k3 - 1 - o]: with w = W transposed per offset [k3, c_out, c_in] and x = gout it is
+ *   dX, on the same map.  bias nullable.  f32 matrix pipe, no atomics, each row written once.
+ * spt_sparse_conv_dw_f32: dw [k3, c_in, c_out], dw[o] = sum over the pairs of o in ascending
+ *   pair order of x[nbr]^T gout[row]: 64 fixed chunks per offset, then added in order.
+ * spt_sparse_conv_dbias_f32: dbias [c_out] = column sums of gout: 1024 fixed row ranges, then
+ *   added in order.
+ * Given a built map, fwd, dw and dbias read nothing back to the host.
+ * ---------------------------------------------------------------------- */
+int spt_sparse_bounds_i32(const int32_t* coords, const int64_t* batch, int64_t n, int64_t* record,
+                          spt_stream_t stream);
+size_t spt_sparse_map_count_workspace_bytes(int64_t n, int key_bits);
+int spt_sparse_map_count(const int32_t* coords, const int64_t* batch, int64_t n,
+                         const int64_t* origin, const int* bits, int kernel_size, int dilation,
+                         uint64_t* skeys, int32_t* sorder, int32_t* rowptr, int64_t* record,
+                         void* ws, size_t ws_bytes, spt_stream_t stream);
+int spt_sparse_map_fill(const int32_t* coords, const int64_t* batch, int64_t n,
+                        const int64_t* origin, const int* bits, int kernel_size, int dilation,
+                        const uint64_t* skeys, const int32_t* sorder, const int32_t* rowptr,
+                        int64_t num_pairs, int32_t* nbr, int32_t* off, int32_t* row,
+                        spt_stream_t stream);
+size_t spt_sparse_map_by_offset_workspace_bytes(int64_t num_pairs);
+int spt_sparse_map_by_offset(const int32_t* off, int64_t num_pairs, int k3, int32_t* perm,
+                             int32_t* optr, void* ws, size_t ws_bytes, spt_stream_t stream);
+int spt_sparse_conv_supported(int c_in, int c_out);
+int spt_sparse_conv_fwd_f32(const float* x, int64_t n, int c_in, const float* w, int k3, int c_out,
+                            const float* bias, const int32_t* rowptr, const int32_t* nbr,
+                            const int32_t* off, int flip, float* out, spt_stream_t stream);
+size_t spt_sparse_conv_dw_workspace_bytes(int k3, int c_in, int c_out);
+int spt_sparse_conv_dw_f32(const float* x, const float* gout, int64_t n, int c_in, int c_out,
+                           int k3, const int32_t* nbr, const int32_t* row, const int32_t* perm,
+                           const int32_t* optr, int64_t num_pairs, float* dw, void* ws,
+                           size_t ws_bytes, spt_stream_t stream);
+size_t spt_sparse_conv_dbias_workspace_bytes(int c_out);
+int spt_sparse_conv_dbias_f32(const float* gout, int64_t n, int c_out, float* dbias, void* ws,
+                              size_t ws_bytes, spt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

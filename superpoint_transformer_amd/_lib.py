@@ -306,6 +306,18 @@ SIGNATURES = {
     "spt_merge_accumulate_f64": (_int, [_p, _i64, _i64, _p, _p, _int, _p, _p, _p, _p, _p, _sz, _p]),
     "spt_edge_weights_workspace_bytes": (_sz, [_i64]),
     "spt_edge_weights_f32": (_int, [_p, _i64, _int, _i64, _p, _i64, _i64, _p, _p, _p, _p, _sz, _p]),
+    "spt_sparse_bounds_i32": (_int, [_p, _p, _i64, _p, _p]),
+    "spt_sparse_map_count_workspace_bytes": (_sz, [_i64, _int]),
+    "spt_sparse_map_count": (_int, [_p, _p, _i64, _p, _p, _int, _int, _p, _p, _p, _p, _p, _sz, _p]),
+    "spt_sparse_map_fill": (_int, [_p, _p, _i64, _p, _p, _int, _int, _p, _p, _p, _i64, _p, _p, _p, _p]),
+    "spt_sparse_map_by_offset_workspace_bytes": (_sz, [_i64]),
+    "spt_sparse_map_by_offset": (_int, [_p, _i64, _int, _p, _p, _p, _sz, _p]),
+    "spt_sparse_conv_supported": (_int, [_int, _int]),
+    "spt_sparse_conv_fwd_f32": (_int, [_p, _i64, _int, _p, _int, _int, _p, _p, _p, _p, _int, _p, _p]),
+    "spt_sparse_conv_dw_workspace_bytes": (_sz, [_int, _int, _int]),
+    "spt_sparse_conv_dw_f32": (_int, [_p, _p, _i64, _int, _int, _int, _p, _p, _p, _p, _i64, _p, _p, _sz, _p]),
+    "spt_sparse_conv_dbias_workspace_bytes": (_sz, [_int]),
+    "spt_sparse_conv_dbias_f32": (_int, [_p, _i64, _int, _p, _p, _sz, _p]),
 }
 
 

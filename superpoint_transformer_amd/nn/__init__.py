@@ -9,6 +9,7 @@ from .mlp import FFN, MLP, Classifier
 from .norm import INDEX_BASED_NORMS, GraphNorm, InstanceNorm, LayerNorm, UnitSphereNorm
 from .pool import (AttentivePool, AttentivePoolWithLearntQueries, BaseAttentivePool, MaxPool,
                    MeanPool, MinPool, StdPool, SumPool, pool_factory)
+from .sparse import ConvBlock, SparseCNN
 from .stage import DownNFuseStage, PointStage, Stage, UpNFuseStage
 from .transformer import TransformerBlock, VersionHolder
 from .unpool import IndexUnpool

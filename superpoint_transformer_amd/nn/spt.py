@@ -121,8 +121,16 @@ class SPT(nn.Module):
                  heads_share_rpe=False, use_pos=True, use_node_hf=True, use_diameter=False,
                  use_diameter_parent=False, pool="max", unpool="index", fusion="cat",
                  norm_mode="graph", output_stage_wise=False, version="3.0.0",
-                 matrix_precision=None, **ignored):
+                 matrix_precision=None, point_cnn_blocks=False, point_cnn=None,
+                 point_cnn_kernel_size=None, point_cnn_dilation=None, point_cnn_norm=None,
+                 point_cnn_activation=None, point_cnn_residual=False,
+                 point_cnn_global_residual=False, point_mlp_on_cnn_feats=False,
+                 post_cnn_point_hf=(), **ignored):
         super().__init__()
+        if point_cnn_blocks and nano:
+            raise ValueError("point_cnn_blocks needs a level-0 stage: not with nano=True")
+        self.point_mlp_on_cnn_feats = point_mlp_on_cnn_feats
+        self.post_cnn_point_hf = list(post_cnn_point_hf or [])
         # not in the reference: "f32" | "bf16" | "f32-exact" pins this model's GEMM precision
         # (precision.matrix_precision, per call); None = whatever is active around the call
         self.matrix_precision = matrix_precision
@@ -182,6 +190,11 @@ class SPT(nn.Module):
             self.first_stage = PointStage(
                 point_mlp, mlp_activation=mlp_activation, mlp_norm=mlp_norm,
                 mlp_drop=point_drop, use_pos=use_pos, use_diameter_parent=use_diameter_parent,
+                cnn_blocks=point_cnn_blocks, cnn=point_cnn,
+                cnn_kernel_size=point_cnn_kernel_size, cnn_dilation=point_cnn_dilation,
+                cnn_norm=point_cnn_norm, cnn_activation=point_cnn_activation,
+                cnn_residual=point_cnn_residual, cnn_global_residual=point_cnn_global_residual,
+                point_mlp_on_cnn_feats=point_mlp_on_cnn_feats,
                 version_holder=self.version_holder)
         if num_down > 0:
             # the per-stage lists keep the length of down_dim: entry 0 is the nano Stage's
@@ -213,6 +226,38 @@ class SPT(nn.Module):
                 for i in range(num_up)])
         else:
             self.up_stages = None
+
+    def _x_mlp(self, data):
+        """The handcrafted features of the first stage's MLP when a CNN is in front
+        (spt.py:777-780): ``x_mlp`` where the level already holds it, else the
+        ``post_cnn_point_hf`` keys concatenated in their order (1-D keys count as one column)."""
+        x_mlp = _get(data, "x_mlp")
+        if x_mlp is not None or not self.post_cnn_point_hf:
+            return x_mlp
+        feats = []
+        for key in self.post_cnn_point_hf:
+            feat = _get(data, key)
+            if feat is None:
+                raise Exception(f"Data should contain the attribute '{key}'")
+            feats.append(feat.unsqueeze(-1) if feat.dim() == 1 else feat)
+        return torch.cat(feats, dim=1)
+
+    @staticmethod
+    def forward_first_stage(data, first_stage, use_node_hf, norm_mode):
+        """spt.py:893-913: the first stage on one level-0 ``Data`` (what
+        ``transforms.PretrainedCNN`` runs outside a model)."""
+        if hasattr(data, "norm_index") and callable(data.norm_index):
+            norm_index = data.norm_index(mode=norm_mode)
+        elif norm_mode == "graph":
+            norm_index = _get(data, "batch")
+        else:
+            raise NotImplementedError("norm_mode != 'graph' needs a Data with norm_index()")
+        return first_stage(
+            _get(data, "x") if use_node_hf else None, norm_index, pos=_get(data, "pos"),
+            diameter=None, node_size=_get(data, "node_size"),
+            super_index=_get(data, "super_index"), edge_index=_get(data, "edge_index"),
+            edge_attr=_get(data, "edge_attr"), coords=_get(data, "coords"),
+            batch=_get(data, "batch"), x_mlp=_get(data, "x_mlp"))
 
     @property
     def num_down_stages(self):
@@ -292,7 +337,8 @@ class SPT(nn.Module):
             _get(d0, "x") if self.use_node_hf else None, norm_index(d0),
             pos=_get(d0, "pos"), node_size=_get(d0, "node_size"),
             super_index=_get(d0, "super_index"), num_super=sizes[1] if len(sizes) > 1 else None,
-            num_graphs=B,
+            num_graphs=B, coords=_get(d0, "coords"), batch=_get(d0, "batch"),
+            x_mlp=self._x_mlp(d0),
             pool_to_parent=(norm_index(levels[1]),) if fuse_pool else None)
 
         down_outputs, node_x, edge_attrs, ea_shares = [], {}, {}, {}

@@ -230,25 +230,64 @@ class UpNFuseStage(Stage):
 
 
 class PointStage(Stage):
-    """Level-0 stage: position injection + point MLP, no attention
-    (stage.py:574-806, ``cnn_blocks=False`` branch; the torchsparse CNN encoder
-    of EZ-SP is outside the hot path)."""
+    """Level-0 stage: position injection + point MLP, no attention (stage.py:574-806).
+    ``cnn_blocks=True`` puts the sparse CNN of EZ-SP (``nn.sparse.SparseCNN`` over the integer
+    ``coords``) in front: with ``point_mlp_on_cnn_feats`` its features (fused with ``x_mlp``) feed
+    the MLP, without it the MLP runs on ``x_mlp`` and the two outputs are concatenated."""
 
     def __init__(self, in_mlp, mlp_activation=nn.LeakyReLU(), mlp_norm=GraphNorm,
                  mlp_drop=None, use_pos=True, use_diameter_parent=False, cnn_blocks=False,
-                 version_holder=None, **unused_cnn_kwargs):
-        if cnn_blocks:
-            raise NotImplementedError("the sparse-CNN point encoder is not on the HIP path")
+                 cnn=(3, 16, 32, 64), cnn_kernel_size=3, cnn_dilation=1, cnn_norm=None,
+                 cnn_activation=None, cnn_residual=False, cnn_global_residual=False,
+                 point_mlp_on_cnn_feats=False, version_holder=None):
         assert in_mlp is None or len(in_mlp) > 1
-        super().__init__(in_mlp[-1] if in_mlp is not None else None, num_blocks=0,
+        if not cnn_blocks:
+            dim = in_mlp[-1] if in_mlp is not None else None
+        else:
+            dim = in_mlp[-1] if in_mlp is not None else \
+                cnn[-1] + 3 * use_pos + use_diameter_parent
+        super().__init__(dim, num_blocks=0,
                          in_mlp=in_mlp, out_mlp=None, mlp_activation=mlp_activation,
                          mlp_norm=mlp_norm, mlp_drop=mlp_drop, use_pos=use_pos,
                          use_diameter=False, use_diameter_parent=use_diameter_parent,
                          version_holder=version_holder)
+        self.point_mlp_on_cnn_feats = point_mlp_on_cnn_feats
+        if cnn_blocks:
+            from .sparse import SparseCNN
+            self.cnn_blocks = SparseCNN(cnn=list(cnn), kernel_size=cnn_kernel_size,
+                                        dilation=cnn_dilation, norm=cnn_norm,
+                                        activation=cnn_activation, residual=cnn_residual,
+                                        global_residual=cnn_global_residual)
+        else:
+            self.cnn_blocks = False
 
     def forward(self, x, norm_index, pos=None, diameter=None, node_size=None,
                 super_index=None, edge_index=None, edge_attr=None, coords=None, batch=None,
                 x_mlp=None, num_super=None, num_graphs=None, pool_to_parent=None):
-        return super().forward(x, norm_index, pos, diameter, node_size, super_index,
-                               edge_index, edge_attr, num_super=num_super,
-                               num_graphs=num_graphs, pool_to_parent=pool_to_parent)
+        if self.cnn_blocks is False:
+            assert self.point_mlp_on_cnn_feats is False, \
+                "Can't use the CNN features as input to the MLP if there is no CNN"
+            return super().forward(x, norm_index, pos, diameter, node_size, super_index,
+                                   edge_index, edge_attr, num_super=num_super,
+                                   num_graphs=num_graphs, pool_to_parent=pool_to_parent)
+        from .sparse import SparseTensor
+        if coords is None:
+            raise ValueError("cnn_blocks=True needs the integer voxel `coords` of the points")
+        if batch is None:
+            batch = torch.zeros(coords.shape[0], dtype=coords.dtype, device=coords.device)
+        coords = torch.cat([batch.view(-1, 1).to(coords.dtype), coords], dim=1)
+        x = self.cnn_blocks(SparseTensor(coords=coords, feats=x), batch=norm_index).F
+        if self.point_mlp_on_cnn_feats:
+            # the MLP's output is the stage's output: the pool-fused route stays correct
+            x = self.feature_fusion(x, x_mlp) if x_mlp is not None else x
+            return super().forward(x, norm_index, pos, diameter, node_size, super_index,
+                                   edge_index, edge_attr, num_super=num_super,
+                                   num_graphs=num_graphs, pool_to_parent=pool_to_parent)
+        assert x_mlp is not None or self.in_mlp is None, \
+            "The MLP in the PointStage needs an input. As `point_mlp_on_cnn_feats` is False, " \
+            "please set some handcrafted features in `post_cnn_point_hf`."
+        # the stage's output is [cnn | mlp]: the pooled MLP output alone would not be it
+        x_mlp, diameter_parent = super().forward(x_mlp, norm_index, pos, diameter, node_size,
+                                                 super_index, edge_index, edge_attr,
+                                                 num_super=num_super, num_graphs=num_graphs)
+        return self.feature_fusion(x, x_mlp), diameter_parent

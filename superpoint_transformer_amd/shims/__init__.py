@@ -1,6 +1,6 @@
 """Import-name shims: the module names the reference imports for this path
 (``torch_scatter``, a subset of ``torch_geometric``, ``src.dependencies.FRNN.frnn``,
-``pgeof``) bound to the HIP kernels, so that the reference's own
+``pgeof``, ``torchsparse``) bound to the HIP kernels, so that the reference's own
 ``src/nn/*.py`` / ``src/utils/*.py`` import and run UNCHANGED on an MI355X.
 
     from superpoint_transformer_amd import shims
@@ -55,6 +55,10 @@ def install(force=False, with_h5py=False):
         "torch_geometric.nn.inits": inits, "torch_geometric.nn.pool": pool,
         "torch_geometric.nn.pool.consecutive": cons,
     })
+    from . import torchsparse_shim                     # (imports nn.sparse: not at module import)
+    ts = _module("torchsparse", __path__=[], SparseTensor=torchsparse_shim.SparseTensor,
+                 nn=torchsparse_shim.nn)
+    table.update({"torchsparse": ts, "torchsparse.nn": torchsparse_shim.nn})
     if with_h5py:
         from . import h5py_shim
         table["h5py"] = h5py_shim

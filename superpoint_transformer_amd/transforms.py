@@ -16,7 +16,7 @@ __all__ = ["horizontal_edge_features", "EDGE_FEATURE_COLUMNS", "NodeSize", "Samp
            "NAGColorAutoContrast", "NAGColorDrop", "GeometricAugmentation", "FeatureAugmentation",
            "ColorAugmentation", "GridSampling3D", "SaveNodeIndex", "NAGSaveNodeIndex", "DataTo",
            "NAGRemoveKeys", "SegmentFeatures", "RadiusHorizontalGraph",
-           "GreedyContourPriorPartition"]
+           "GreedyContourPriorPartition", "QuantizePointCoordinates", "PretrainedCNN"]
 
 EDGE_FEATURE_COLUMNS = [
     "mean_off_x", "mean_off_y", "mean_off_z", "std_off_x", "std_off_y", "std_off_z",
@@ -1484,3 +1484,87 @@ class ColorAugmentation:
 
     def __call__(self, nag):
         return self.apply(nag, self.draw(nag))
+
+
+class QuantizePointCoordinates:
+    """``QuantizePointCoordinates`` (src/transforms/sampling.py:507-568): the integer voxel
+    coordinates the sparse CNN runs on, computed on the fly because the augmentations move the
+    points.  ``size <= 0``: nothing happens.  Otherwise one point per voxel of ``size`` is kept -
+    ``voxel.voxel_groups(pos, size, batch).last``, the highest point index of each voxel in
+    ascending voxel order (PyG's ``consecutive_cluster`` on the CPU) - through
+    ``nag.select(0, ...)``, and level 0 gets ``coords`` = ``round(pos / size)`` of the kept points
+    as floats, shifted to a zero minimum per axis unless ``allow_negative_coords``."""
+
+    def __init__(self, size, allow_negative_coords=False):
+        self.grid_size = size
+        self.allow_negative_coords = allow_negative_coords
+
+    def __call__(self, nag):
+        if self.grid_size <= 0:
+            return nag
+        from .voxel import voxel_groups
+        data = nag[0]
+        pos = data.pos
+        kept = voxel_groups(pos, self.grid_size, data.get("batch")).last
+        coords = torch.round(pos / self.grid_size)[kept]
+        out = nag.select(0, kept)
+        if not self.allow_negative_coords:
+            coords = coords - coords.min(dim=0, keepdim=True).values
+        out[0].coords = coords
+        return out
+
+
+class PretrainedCNN:
+    """``PretrainedCNN`` (src/transforms/point.py:630-770): runs a trained first stage (a
+    ``PointStage`` with ``cnn_blocks=True``) over a level-0 ``Data`` at preprocessing time and
+    leaves its output in ``data.x``, the features the partition reads.  ``load_checkpoint`` takes
+    the keys of ``checkpoint['state_dict']`` that contain ``first_stage``, strips
+    ``net.first_stage.`` and raises ``ValueError`` on a shape mismatch; keys the module lacks are
+    left out, parameters the checkpoint lacks keep their values."""
+
+    def __init__(self, first_stage, ckpt_path, partition_hf=None, norm_mode="graph", device="cuda",
+                 verbose=False):
+        assert partition_hf is not None, "`partition_hf` has not been set up."
+        self.norm_mode, self.ckpt_path, self.partition_hf = norm_mode, ckpt_path, partition_hf
+        self.device, self.verbose = device, verbose
+        first_stage.to(device)
+        self.first_stage = self.load_checkpoint(first_stage, ckpt_path, device, verbose=verbose)
+
+    def __call__(self, data):
+        from .nn.spt import SPT
+        with torch.no_grad():
+            # the partition_hf keys stay: they are saved to disk for training
+            data.add_keys_to(keys=self.partition_hf, to="x", delete_after=False)
+            x, _ = SPT.forward_first_stage(data=data, first_stage=self.first_stage,
+                                           use_node_hf=True, norm_mode=self.norm_mode)
+            data.x = x
+        return data
+
+    _process = __call__
+
+    @staticmethod
+    def load_checkpoint(first_stage, ckpt_path, device, verbose=False):
+        import os
+        assert ckpt_path is not None and os.path.exists(ckpt_path), \
+            f"Expected a valid checkpoint path. Received {ckpt_path=}"
+        checkpoint = torch.load(ckpt_path, map_location=device)
+        model_dict = first_stage.state_dict()
+        ckpt_dict = {k.replace("net.first_stage.", ""): v
+                     for k, v in checkpoint["state_dict"].items() if "first_stage" in k}
+        loadable, unused = {}, {}
+        for k, v in ckpt_dict.items():
+            if k not in model_dict:
+                unused[k] = v
+            elif v.shape != model_dict[k].shape:
+                raise ValueError(f"Shape mismatch for {k}: checkpoint {v.shape} vs model "
+                                 f"{model_dict[k].shape}")
+            else:
+                loadable[k] = v
+        missing = [k for k in model_dict if k not in loadable]
+        model_dict.update(loadable)
+        first_stage.load_state_dict(model_dict)
+        if verbose:
+            print(f"PretrainedCNN: loaded {len(loadable)} parameters ({', '.join(loadable)}); "
+                  f"{len(unused)} unused in the checkpoint ({', '.join(unused)}); {len(missing)} "
+                  f"missing from it ({', '.join(missing)})")
+        return first_stage
