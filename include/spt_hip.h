@@ -117,6 +117,22 @@ int spt_csr_pos_seg(const int32_t* rowptr, int64_t num_seg, int64_t n, int32_t* 
                     spt_stream_t stream);
 int spt_csr_gather_i64_i32(const int64_t* src, const int32_t* perm, int64_t n, int32_t* out,
                            spt_stream_t stream);
+/* The by-source view of an attention graph and every table a level's attention calls derive from
+ * it, in one entry (11 launches for the three sort passes of 17 .. 24 key bits; the entries above
+ * and spt_attn_mirror_prepare / spt_attn_pack_tile_ids_mirror took about 22 for the same arrays,
+ * bit for bit).
+ * `edge_index` = the [2, e] int64 list (e >= 1), n = the number of nodes, `pairs` = M of a list
+ * declared [i<j | j>i | loops] (see spt_attn_mirror_prepare) or -1.  Written, all int32:
+ * erowptr [n + 1], eperm [e] (the stable order by source), tgt_sorted [e] = edge_index[1][eperm],
+ * src_sorted [e] = edge_index[0][eperm], inv [e] = the inverse of eperm (NULL: not wanted),
+ * tile_ids [ceil(e / 16), 64] = the records of spt_attn_pack_tile_ids_mirror (NULL: not wanted;
+ * needs pairs >= 0 and inv), *flag = the verdict of the mirror check (same bits; 0 for
+ * pairs = -1) - WRITTEN, not OR-ed: the caller does not clear it. */
+size_t spt_edge_csr_build_workspace_bytes(int64_t e, int64_t n);
+int spt_edge_csr_build(const int64_t* edge_index, int64_t e, int64_t n, int64_t pairs,
+                       int32_t* erowptr, int32_t* eperm, int32_t* tgt_sorted, int32_t* src_sorted,
+                       int32_t* inv, int32_t* tile_ids, int32_t* flag, void* ws, size_t ws_bytes,
+                       spt_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Segment reduce  out[s,:] = reduce_{i in seg s} x[i,:]      (a1, a4, a8)

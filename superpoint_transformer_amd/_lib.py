@@ -29,6 +29,8 @@ SIGNATURES = {
     "spt_csr_build": (_int, [_p, _i64, _i64, _p, _p, _p, _sz, _p]),
     "spt_csr_pos_seg": (_int, [_p, _i64, _i64, _p, _p]),
     "spt_csr_gather_i64_i32": (_int, [_p, _p, _i64, _p, _p]),
+    "spt_edge_csr_build_workspace_bytes": (_sz, [_i64, _i64]),
+    "spt_edge_csr_build": (_int, [_p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "spt_segcsr_reduce_f32": (_int, [_int, _p, _p, _p, _i64, _i64, _int, _p, _p, _p]),
     "spt_segcsr_max_affine_f32": (_int, [_p, _p, _p, _i64, _i64, _int, _p, _p, _p, _f32, _p, _p, _p, _p]),
     "spt_segcsr_max_affine_bf16_supported": (_int, [_int, _i64]),

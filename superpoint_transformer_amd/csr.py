@@ -9,6 +9,7 @@ the pool, UnitSphereNorm, unpool-backward and softmax-group uses of one
 (``Tensor._version``) and dies with the tensor object - it is never keyed on
 ``data_ptr`` alone (the caching allocator recycles addresses).
 """
+import os
 import weakref
 
 import torch
@@ -99,6 +100,17 @@ def csr_of(idx, num_seg=None):
 
 _USE_SUB_VIEWS = True
 _USE_MIRROR = True
+_USE_FUSED_EDGE = os.environ.get("SPT_EDGE_CSR_FUSED", "1") != "0"
+
+
+def use_fused_edge_build(on=True):
+    """Whether ``edge_csr_of`` builds an attention graph's tables with the one entry
+    ``spt_edge_csr_build`` (default; ``SPT_EDGE_CSR_FUSED=0`` starts a process with it off) or with
+    ``spt_csr_build`` and one kernel per table.  The tables are the same arrays bit for bit.
+    Returns the old setting."""
+    global _USE_FUSED_EDGE
+    old, _USE_FUSED_EDGE = _USE_FUSED_EDGE, bool(on)
+    return old
 
 
 def use_mirror_views(on=True):
@@ -325,7 +337,7 @@ class EdgeCSR:
     edge_index[1] in CSR order."""
 
     __slots__ = ("erowptr", "eperm", "tgt_sorted", "n", "e", "_view", "_src_sorted", "_tview",
-                 "_tile_ids", "_ei", "_mirror", "_ei_ref")
+                 "_tile_ids", "_ei", "_mirror", "_ei_ref", "_inv", "_flag")
 
     def __init__(self, erowptr, eperm, tgt_sorted, n, e, view=None, edge_index=None):
         self.erowptr, self.eperm, self.tgt_sorted, self.n, self.e = \
@@ -340,6 +352,7 @@ class EdgeCSR:
         # then come from the by-source view alone (no second sort); the structure is checked on
         # the device (spt_attn_mirror_prepare) and a wrong hint raises StaleCSRError.
         self._ei = self._mirror = self._ei_ref = None
+        self._inv = self._flag = None      # inverse of eperm / device verdict of the mirror check, once built
         m = getattr(edge_index, MIRROR_ATTR, None) if edge_index is not None else None
         if (_USE_MIRROR and m is not None and edge_index._version == 0 and edge_index.dtype == torch.int64
                 and edge_index.is_contiguous() and edge_index.dim() == 2 and 0 <= 2 * int(m) <= e):
@@ -397,6 +410,11 @@ class EdgeCSR:
                 _lib.ptr(self.eperm), _lib.ptr(self.tgt_sorted), _lib.ptr(src), _lib.ptr(inv), self.e,
                 self._mirror, _lib.ptr(out), sp)
             _lib.check(st, "spt_attn_pack_tile_ids_mirror")
+        self._inv = inv[:self.e]
+        self._defer_mirror_verdict(flag, dev)
+
+    def _defer_mirror_verdict(self, flag, dev):
+        self._flag = flag
         what = f"an edge list of {self.e} edges ({self._mirror} pairs)"
         if torch.cuda.is_current_stream_capturing():
             _PENDING.append((None, flag, what, self._ei_ref, "mirror", None))
@@ -437,6 +455,9 @@ def edge_csr_of(edge_index, num_nodes):
     key = (edge_index._version, int(num_nodes), edge_index.data_ptr(), edge_index.shape[1])
     if memo is not None and key in memo:
         return memo[key]
+    if _USE_FUSED_EDGE and edge_index.dim() == 2 and edge_index.shape[1] > 0:
+        ecsr = _edge_csr_fused(edge_index, num_nodes)
+        return _memoise_edge(edge_index, memo, key, ecsr)
     view = build_csr(edge_index[0], num_nodes)
     # plumbing: the targets in CSR order (one gather per batch and level)
     e = edge_index.shape[1]
@@ -450,6 +471,10 @@ def edge_csr_of(edge_index, num_nodes):
         verify_adopted()              # (a level without `sub` never reaches adopt_csr's own reading)
     ecsr = EdgeCSR(view.rowptr, view.perm, tgt_sorted, int(num_nodes), edge_index.shape[1], view,
                    edge_index=edge_index)
+    return _memoise_edge(edge_index, memo, key, ecsr)
+
+
+def _memoise_edge(edge_index, memo, key, ecsr):
     if memo is None or any(k[0] != edge_index._version for k in memo):
         memo = {}
         try:
@@ -457,6 +482,41 @@ def edge_csr_of(edge_index, num_nodes):
         except Exception:
             return ecsr
     memo[key] = ecsr
+    return ecsr
+
+
+def _edge_csr_fused(edge_index, num_nodes):
+    """``EdgeCSR`` through ``spt_edge_csr_build``: the sort by source, ``tgt_sorted``,
+    ``src_sorted`` and - for a list that declares its mirror structure while the process builds
+    target-order records - the structure check, the inverse of ``eperm`` and the tile records, in
+    one call.  The verdict of the check is deferred exactly as ``EdgeCSR._pack_mirror`` defers it."""
+    _lib.require_cuda(edge_index)
+    dev = edge_index.device
+    e, n = edge_index.shape[1], max(int(num_nodes), 1)
+    ei = _lib.dense(edge_index, torch.int64, 8)
+    i32 = dict(dtype=torch.int32, device=dev)
+    erowptr = torch.empty(n + 1, **i32)
+    eperm, tgt_sorted, src_sorted = (torch.empty(e, **i32) for _ in range(3))
+    if _PENDING and not torch.cuda.is_current_stream_capturing():
+        verify_adopted()
+    ecsr = EdgeCSR(erowptr, eperm, tgt_sorted, int(num_nodes), e, None, edge_index=edge_index)
+    records = ecsr._mirror is not None and int(_lib.lib.spt_attn_tile_record_ints_m(-1)) == 64
+    inv = torch.empty(e, **i32) if records else None
+    ids = torch.empty(((e + 15) // 16, 64), **i32) if records else None
+    flag = torch.empty(1, **i32)
+    ws_bytes = _lib.lib.spt_edge_csr_build_workspace_bytes(e, n)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        st = _lib.lib.spt_edge_csr_build(
+            _lib.ptr(ei), e, n, ecsr._mirror if records else -1, _lib.ptr(erowptr), _lib.ptr(eperm),
+            _lib.ptr(tgt_sorted), _lib.ptr(src_sorted), _lib.ptr(inv), _lib.ptr(ids), _lib.ptr(flag),
+            _lib.ptr(ws), ws_bytes, _lib.stream_ptr(dev))
+    _lib.check(st, "spt_edge_csr_build")
+    ecsr._src_sorted = src_sorted
+    if records:
+        ecsr._inv = inv
+        ecsr._tile_ids = {64: ids}
+        ecsr._defer_mirror_verdict(flag, dev)
     return ecsr
 
 

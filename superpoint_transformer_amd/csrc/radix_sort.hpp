@@ -368,4 +368,215 @@ static inline int radix_sort_pairs(const int64_t* idx64, const uint32_t* keys32,
   return 0;
 }
 
+// ---- the edge sort: (key, value, target) triples, tables out of the last pass ---------------------
+// The sort of an attention graph's edges by source (csr_build.hip: spt_edge_csr_build).  Same
+// tile, same (wave, round, lane) order, same ballot ranking and the same <= 8-bit balanced digits
+// as above, so it is stable and gives the one result the pair sort gives.  What differs:
+//   * the per-workgroup histograms [digit][workgroup] are scanned ROW BY ROW by one launch
+//     (edge_rowscan_kernel: a workgroup per digit, which also leaves the digit's total); the
+//     scatter kernel scans the <= 256 digit totals itself to find where a digit starts.  One scan
+//     launch per pass instead of three, no partials region;
+//   * the first histogram kernel reads the int64 sources and, when the caller declared a mirror
+//     count, checks that structure on the way (one verdict word per workgroup, OR-ed by the row
+//     scan: no atomics on the flag, nothing to clear);
+//   * the scatter kernel puts its tile in digit order in LDS before it writes, so the elements
+//     of one digit leave as ONE run of consecutive addresses from consecutive lanes (a store
+//     per input element touched up to 64 lines per instruction: 76 - 136 us per pass over 7 M
+//     edges for pairs, against 62 - 70 us staged for triples);
+//   * the target of every edge travels with it (read once, in order, by the first pass), so the
+//     last pass writes tgt_sorted without a random 8-byte gather; it also writes inv[value].
+// Wider digits (up to 11 bits: two passes for 2^19 nodes) were built and measured: the last pass
+// then took 235 us against 83 us (runs of 4 elements per digit and tile), 583 against 527 us
+// per level-1 build - three passes stay.
+
+// FIRST: keys = (u32) ei[0 .. n), checks [i<j | j>i | loops] with `pairs` = M (< 0: no check).
+template <bool FIRST>
+__global__ __launch_bounds__(SORT_THREADS) void edge_hist_kernel(
+    const int64_t* __restrict__ ei, const uint32_t* __restrict__ keys_in, int64_t n, int shift,
+    int bits, uint32_t* __restrict__ blockhist, int nblocks, int64_t pairs,
+    uint32_t* __restrict__ blockbad) {
+  __shared__ uint32_t h[MAX_BINS];
+  __shared__ uint32_t sbad;
+  h[threadIdx.x] = 0;
+  if (threadIdx.x == 0) sbad = 0;
+  __syncthreads();
+  const int64_t base = (int64_t)blockIdx.x * SORT_TILE;
+  const uint32_t mask = (1u << bits) - 1u;
+  uint32_t bad = 0;
+#pragma unroll
+  for (int k = 0; k < SORT_ITEMS; ++k) {
+    const int64_t i = base + (int64_t)k * SORT_THREADS + threadIdx.x;
+    if (i < n) {
+      uint32_t key;
+      if constexpr (FIRST) {
+        const int64_t s = ei[i];
+        key = (uint32_t)s;
+        if (pairs >= 0) {
+          const int64_t t = ei[n + i];
+          if (i < pairs) {
+            if (ei[i + pairs] != t || ei[n + i + pairs] != s) bad |= 1u;
+          } else if (i >= 2 * pairs) {
+            if (s != t) bad |= 2u;
+          }
+        }
+      } else {
+        key = keys_in[i];
+      }
+      atomicAdd(&h[(key >> shift) & mask], 1u);
+    }
+  }
+  if constexpr (FIRST)
+    if (bad) atomicOr(&sbad, bad);
+  __syncthreads();
+  if ((int)threadIdx.x < (1 << bits))
+    blockhist[(size_t)threadIdx.x * nblocks + blockIdx.x] = h[threadIdx.x];
+  if constexpr (FIRST)
+    if (threadIdx.x == 0) blockbad[blockIdx.x] = sbad;
+}
+
+// Workgroup d: exclusive scan of row d of blockhist in place, the row's total to digit_total[d].
+// Workgroup 0 also ORs the per-workgroup verdicts into *flag (flag == nullptr: no verdicts).
+static __global__ __launch_bounds__(SCAN_THREADS) void edge_rowscan_kernel(
+    uint32_t* __restrict__ blockhist, int nblocks, uint32_t* __restrict__ digit_total,
+    const uint32_t* __restrict__ blockbad, int32_t* __restrict__ flag) {
+  uint32_t* row = blockhist + (size_t)blockIdx.x * nblocks;
+  uint32_t carry = 0;
+  for (int base = 0; base < nblocks; base += SCAN_THREADS) {
+    const int i = base + threadIdx.x;
+    const uint32_t v = (i < nblocks) ? row[i] : 0u;
+    uint32_t tot;
+    const uint32_t ex = block_exclusive_scan(v, &tot);
+    if (i < nblocks) row[i] = carry + ex;
+    carry += tot;
+  }
+  if (threadIdx.x == 0) digit_total[blockIdx.x] = carry;
+  if (blockIdx.x == 0 && flag) {
+    __shared__ uint32_t sbad;
+    if (threadIdx.x == 0) sbad = 0;
+    __syncthreads();
+    uint32_t bad = 0;
+    for (int i = threadIdx.x; i < nblocks; i += SCAN_THREADS) bad |= blockbad[i];
+    if (bad) atomicOr(&sbad, bad);
+    __syncthreads();
+    if (threadIdx.x == 0) *flag = (int32_t)sbad;
+  }
+}
+
+// MODE 1: key = (u32) ei[i], value = i, target = (i32) ei[n + i];  MODE 0: the three input arrays.
+// LAST: also inv[value] = destination (inv may be null).
+template <int MODE, bool LAST>
+__global__ __launch_bounds__(SORT_THREADS) void edge_scatter_kernel(
+    const int64_t* __restrict__ ei, const uint32_t* __restrict__ keys_in,
+    const uint32_t* __restrict__ vals_in, const int32_t* __restrict__ tgts_in, int64_t n, int shift,
+    int bits, const uint32_t* __restrict__ blockoff, const uint32_t* __restrict__ digit_total,
+    int nblocks, uint32_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out,
+    int32_t* __restrict__ tgts_out, int32_t* __restrict__ inv) {
+  // the counters [wave][MAX_BINS]; once every element knows its slot, the staged tile
+  // (keys | values | targets) takes over their words
+  __shared__ uint32_t buf[3 * SORT_TILE];
+  __shared__ uint32_t dbase[MAX_BINS];  // where a digit starts; later: destination - slot of the digit
+  __shared__ uint32_t texcl[MAX_BINS];  // first slot of a digit in the staged tile
+  static_assert(SORT_WAVES * MAX_BINS <= 3 * SORT_TILE && MAX_BINS == SORT_THREADS, "LDS plan");
+  uint32_t(*cnt)[MAX_BINS] = reinterpret_cast<uint32_t(*)[MAX_BINS]>(buf);
+  const int w = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
+  const int bins = 1 << bits;
+  const bool own = (int)threadIdx.x < bins;     // this thread owns digit threadIdx.x
+  for (int j = threadIdx.x; j < SORT_WAVES * MAX_BINS; j += SORT_THREADS) buf[j] = 0;
+
+  const int64_t tbase = (int64_t)blockIdx.x * SORT_TILE;
+  const int64_t wbase = tbase + (int64_t)w * WAVE_CHUNK;
+  const uint32_t mask = (uint32_t)bins - 1u;
+  const uint64_t lt = lanemask_lt();
+
+  uint32_t key[SORT_ITEMS];
+  uint32_t val[SORT_ITEMS];
+  int32_t tgt[SORT_ITEMS];
+  uint32_t rank[SORT_ITEMS];
+#pragma unroll
+  for (int r = 0; r < SORT_ITEMS; ++r) {
+    const int64_t i = wbase + r * 64 + lane;
+    const bool valid = i < n;
+    if constexpr (MODE == 1) {
+      key[r] = valid ? (uint32_t)ei[i] : 0xffffffffu;
+      val[r] = (uint32_t)i;
+      tgt[r] = valid ? (int32_t)ei[n + i] : 0;
+    } else {
+      key[r] = valid ? keys_in[i] : 0xffffffffu;
+      val[r] = valid ? vals_in[i] : 0u;
+      tgt[r] = valid ? tgts_in[i] : 0;
+    }
+  }
+  {  // where every digit starts: exclusive scan of the digit totals (its barriers cover the clearing)
+    const uint32_t t = own ? digit_total[threadIdx.x] : 0u;
+    const uint32_t ex = block_exclusive_scan(t, nullptr);
+    if (own) dbase[threadIdx.x] = ex;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < SORT_ITEMS; ++r) {
+    const int64_t i = wbase + r * 64 + lane;
+    const bool valid = i < n;
+    const uint32_t d = (key[r] >> shift) & mask;
+    uint64_t peers = __ballot(valid);
+    for (int b = 0; b < bits; ++b) {
+      const bool bit = (d >> b) & 1u;
+      const uint64_t m = __ballot(valid && bit);
+      peers &= bit ? m : ~m;
+    }
+    const uint32_t pre = cnt[w][d];
+    const uint32_t rk = __popcll(peers & lt);
+    const uint32_t tot = __popcll(peers);
+    rank[r] = pre + rk;
+    __builtin_amdgcn_wave_barrier();
+    if (valid && rk == tot - 1) cnt[w][d] = pre + tot;  // highest peer lane
+    __builtin_amdgcn_wave_barrier();
+  }
+  __syncthreads();
+  {  // per digit: the waves' offsets inside it, its first slot in the tile, destination - slot
+    uint32_t tc = 0;
+    if (own) {
+#pragma unroll
+      for (int w2 = 0; w2 < SORT_WAVES; ++w2) {
+        const uint32_t t = cnt[w2][threadIdx.x];
+        cnt[w2][threadIdx.x] = tc;
+        tc += t;
+      }
+    }
+    const uint32_t ex = block_exclusive_scan(tc, nullptr);
+    if (own) {
+      texcl[threadIdx.x] = ex;
+      dbase[threadIdx.x] += blockoff[(size_t)threadIdx.x * nblocks + blockIdx.x] - ex;   // (mod 2^32)
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < SORT_ITEMS; ++r) {   // every element's slot, before the counters' words are reused
+    const uint32_t d = (key[r] >> shift) & mask;
+    rank[r] += texcl[d] + cnt[w][d];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < SORT_ITEMS; ++r) {
+    const int64_t i = wbase + r * 64 + lane;
+    if (i < n) {
+      buf[rank[r]] = key[r];
+      buf[SORT_TILE + rank[r]] = val[r];
+      buf[2 * SORT_TILE + rank[r]] = (uint32_t)tgt[r];
+    }
+  }
+  __syncthreads();
+  const int tn = (int)((n - tbase) < (int64_t)SORT_TILE ? (n - tbase) : (int64_t)SORT_TILE);
+  for (int j = threadIdx.x; j < tn; j += SORT_THREADS) {
+    const uint32_t k = buf[j];
+    const uint32_t v = buf[SORT_TILE + j];
+    const uint32_t dst = dbase[(k >> shift) & mask] + (uint32_t)j;
+    keys_out[dst] = k;
+    vals_out[dst] = v;
+    tgts_out[dst] = (int32_t)buf[2 * SORT_TILE + j];
+    if constexpr (LAST)
+      if (inv) inv[v] = (int32_t)dst;
+  }
+}
+
 }  // namespace spt
