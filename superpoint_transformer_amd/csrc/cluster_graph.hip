@@ -8,8 +8,8 @@
 //    removal, to_trimmed (src/utils/graph.py:466-502: flip to s < t, coalesce with
 //    reduce='min', drop self loops) or plain coalesce.  The reference runs ~10 boolean
 //    indexing / vstack passes and a torch_geometric coalesce (sort + scatter); here one
-//    key-generation kernel, two stable radix sorts (by t, then by s), a run-head flag
-//    kernel, a scan and one compaction.
+//    key-generation kernel, the wide-key sort and run flags of sorted_runs.hpp (two stable
+//    radix sorts, by t, then by s; a run-head flag kernel; a scan) and one compaction.
 //
 //  * spt_cluster_pair_anchors_f32 - scatter_nearest_neighbor (src/utils/scatter.py:128-238)
 //    + the anchor distance (neighbors.py:631-632).  The reference expands EVERY edge into
@@ -17,7 +17,7 @@
 //    22-77: E x mean cluster size rows, chunked to survive) and runs 2 x cycles scatter_min
 //    over it.  Here a lane group owns an edge and walks the two clusters through the CSR
 //    view of the point->cluster index; nothing is materialised.
-#include "radix_sort.hpp"
+#include "sorted_runs.hpp"
 
 namespace spt {
 namespace cgraph {
@@ -41,32 +41,8 @@ __global__ void candidate_keys_kernel(const int64_t* __restrict__ nn,
   }
 }
 
-__global__ void gather_u32_kernel(const uint32_t* __restrict__ src,
-                                  const uint32_t* __restrict__ order, int64_t m,
-                                  uint32_t* __restrict__ dst) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < m; p += stride)
-    dst[p] = src[order[p]];
-}
-
-// flag[p] = 1 where sorted position p starts a run of equal (lo, hi) and is not rejected
-__global__ void run_heads_kernel(const uint32_t* __restrict__ lo, const uint32_t* __restrict__ hi,
-                                 const uint32_t* __restrict__ order, int64_t m, int64_t S,
-                                 uint32_t* __restrict__ flag) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p <= m; p += stride) {
-    if (p == m) { flag[p] = 0; continue; }                            // slot for the total
-    const uint32_t v = order[p];
-    const uint32_t a = lo[v], b = hi[v];
-    bool head = (int64_t)a < S;
-    if (head && p > 0) {
-      const uint32_t u = order[p - 1];
-      head = lo[u] != a || hi[u] != b;
-    }
-    flag[p] = head ? 1u : 0u;
-  }
-}
-
+// lo / hi: the unsorted candidates; order and pos: the permutation and the scanned run flags of
+// csrc/sorted_runs.hpp (lo the major word, hi the minor one, S the limit)
 __global__ void emit_edges_kernel(const uint32_t* __restrict__ lo, const uint32_t* __restrict__ hi,
                                   const uint32_t* __restrict__ order,
                                   const uint32_t* __restrict__ pos, const float* __restrict__ dist,
@@ -91,26 +67,9 @@ __global__ void emit_edges_kernel(const uint32_t* __restrict__ lo, const uint32_
   }
 }
 
-struct Plan {
-  size_t off_lo, off_hi, off_key, off_flag, off_sort, off_part, total;
-  int64_t part_cap;
-};
-
-static Plan make_plan(int64_t m) {
-  Plan p;
-  size_t o = 0;
-  const int64_t mm = m > 0 ? m : 1;
-  p.off_lo = o;   o += align_up((size_t)mm * 4, 256);
-  p.off_hi = o;   o += align_up((size_t)mm * 4, 256);
-  p.off_key = o;  o += align_up((size_t)mm * 4, 256);
-  p.off_flag = o; o += align_up((size_t)(mm + 1) * 4, 256);
-  p.off_sort = o; o += RadixScratch::bytes(m + 1);
-  p.off_part = o; o += scan_part_bytes(mm + 1);   // scan of flag[0..m]: the sort's partials only
-                                                  // cover its digit histograms
-  p.part_cap = (int64_t)((o - p.off_part) / 4);
-  p.total = o;
-  return p;
-}
+// The whole scratch is the shared plan, without run starts: the unsorted lo word stays whole for
+// emit_edges_kernel.  Its size does not depend on the bits, which the entry knows only with S.
+static RunsPlan make_plan(int64_t m, int bits) { return runs_plan(m, bits, bits, false); }
 
 // ---- nearest anchors ---------------------------------------------------------------
 __device__ __forceinline__ uint32_t ordered_bits(float f) {
@@ -186,7 +145,7 @@ using namespace spt::cgraph;
 
 extern "C" size_t spt_cluster_graph_edges_workspace_bytes(int64_t num_clusters, int k) {
   if (num_clusters < 0 || k < 1) return 0;
-  return make_plan(num_clusters * k).total;
+  return make_plan(num_clusters * k, 1).total;
 }
 
 extern "C" int spt_cluster_graph_edges(const int64_t* neighbors, const float* distances,
@@ -203,36 +162,21 @@ extern "C" int spt_cluster_graph_edges(const int64_t* neighbors, const float* di
     return 0;
   }
   SPT_CHECK_ARG(neighbors && distances && r_cluster && edges && edge_dist, "null pointer");
-  const Plan p = make_plan(m);
+  const RunsPlan p = make_plan(m, bits_for(S + 1));
   SPT_CHECK_ARG(ws_bytes >= p.total && ws, "workspace too small");
   char* base = (char*)ws;
-  uint32_t* lo = (uint32_t*)(base + p.off_lo);
-  uint32_t* hi = (uint32_t*)(base + p.off_hi);
-  uint32_t* key = (uint32_t*)(base + p.off_key);
-  uint32_t* flag = (uint32_t*)(base + p.off_flag);
-  uint32_t* part = (uint32_t*)(base + p.off_part);
-  RadixScratch s;
-  s.carve(base + p.off_sort, m + 1);
+  Runs r = runs_carve(base, p, m);
+  uint32_t *lo = r.in.major, *hi = r.in.minor;                        // lexicographic (lo, hi)
 
   const float gap_term = (float)(1.732 * (double)gap);                // neighbors.py:592
   const int g = stream_grid(m, 256);
   candidate_keys_kernel<<<g, 256, 0, stream>>>(neighbors, distances, r_cluster, S, k, gap_term,
                                                trim, lo, hi);
-  // lexicographic (lo, hi): LSD = stable sort by hi, then stable sort by lo
-  const int nb = bits_for(S + 1);
-  const uint32_t *ks, *vs;
-  SPT_CHECK_ARG(radix_sort_pairs<2>(nullptr, hi, nullptr, m, nb, s, nullptr, &ks, &vs, stream) == 0,
+  SPT_CHECK_ARG(sort_runs(base, p, r, m, stream) == 0, "scan partials do not fit their region");
+  SPT_CHECK_ARG(flag_runs(base, p, r, m, (uint64_t)S, stream) == 0,
                 "scan partials do not fit their region");
-  gather_u32_kernel<<<g, 256, 0, stream>>>(lo, vs, m, key);
-  RadixScratch s2 = s;
-  if (vs == s.v0) { s2.v0 = s.v1; s2.v1 = s.v0; }
-  SPT_CHECK_ARG(radix_sort_pairs<0>(nullptr, key, vs, m, nb, s2, nullptr, &ks, &vs, stream) == 0,
-                "scan partials do not fit their region");
-  run_heads_kernel<<<stream_grid(m + 1, 256), 256, 0, stream>>>(lo, hi, vs, m, S, flag);
-  SPT_CHECK_ARG(device_exclusive_scan(flag, m + 1, part, p.part_cap, stream) == 0,
-                "scan partials do not fit their region");
-  emit_edges_kernel<<<g, 256, 0, stream>>>(lo, hi, vs, flag, distances, m, S, m, edges,
-                                           edge_dist, count);
+  emit_edges_kernel<<<g, 256, 0, stream>>>(lo, hi, r.sorted.order, r.excl, distances, m, S, m,
+                                           edges, edge_dist, count);
   SPT_CHECK_LAUNCH();
   return 0;
 }

@@ -10,9 +10,9 @@
 // agree with it label for label and bit for bit.
 //
 //   spt_component_graph_f32   quotient of an edge list under a relabelling: pairs ordered
-//                             lo < hi, self loops dropped, one stable LSD radix sort of
-//                             (lo << 32 | hi) over the bits the key needs, run heads by the
-//                             device scan, duplicate weights reduced in input order
+//                             lo < hi, self loops dropped, the runs of equal (lo, hi) by the
+//                             wide-key sort of sorted_runs.hpp (dropped edges in its tail),
+//                             duplicate weights reduced in input order
 //   spt_merge_means_f64       m_c = F_c / s_c
 //   spt_merge_choose_f64      one lane per edge: gain of the merge, 64-bit atomic min of
 //                             (orderable gain << 32 | partner) at both ends
@@ -24,9 +24,10 @@
 //
 // Nothing here adds floats atomically: every float result is a function of the input alone.
 // Sums over more than LONG_RUN members are 64 strided partial sums (lane l takes members
-// l, l + 64, ...) combined by the fixed xor tree, as in voxel.hip; shorter ones are serial.
+// l, l + 64, ...) combined by the fixed xor tree, like the per-voxel means of voxel.hip; shorter
+// ones are serial.
 // The build sets -ffp-contract=off and no fma is written: a * b + c rounds twice, as numpy does.
-#include "radix_sort.hpp"
+#include "sorted_runs.hpp"
 
 namespace spt {
 namespace merge {
@@ -84,55 +85,19 @@ __global__ __launch_bounds__(THREADS) void key_kernel(
   }
 }
 
-__global__ __launch_bounds__(THREADS) void gather_u32_kernel(
-    const uint32_t* __restrict__ src, const uint32_t* __restrict__ perm, int64_t n,
-    uint32_t* __restrict__ out) {
-  const int64_t step = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step)
-    out[i] = src[perm[i]];
-}
-
-// flags [E + 1]: 1 at the first position of every run of equal (lo, hi) among the kept edges;
-// shi [E] = the larger end point in sorted order
-__global__ __launch_bounds__(THREADS) void heads_kernel(
-    const uint32_t* __restrict__ slo, const uint32_t* __restrict__ khi,
-    const uint32_t* __restrict__ perm, int64_t E, uint32_t C, uint32_t* __restrict__ shi,
-    uint32_t* __restrict__ flags) {
-  const int64_t step = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= E; i += step) {
-    if (i == E) { flags[E] = 0; continue; }
-    const uint32_t lo = slo[i], hi = khi[perm[i]];
-    shi[i] = hi;
-    bool head = lo < C;
-    if (head && i > 0) head = slo[i - 1] != lo || khi[perm[i - 1]] != hi;
-    flags[i] = head ? 1u : 0u;
-  }
-}
-
-// ranks [E + 1] = exclusive scan of the flags.  starts [R + 1]: first position of every run, and
-// the number of kept edges behind the last one.
-__global__ __launch_bounds__(THREADS) void starts_kernel(
-    const uint32_t* __restrict__ slo, const uint32_t* __restrict__ ranks, int64_t E, uint32_t C,
-    uint32_t* __restrict__ starts, int64_t* __restrict__ count) {
-  const int64_t step = (int64_t)gridDim.x * blockDim.x;
-  const uint32_t R = ranks[E];
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= E; i += step) {
-    const bool kept = i < E && slo[i] < C;
-    const bool prev_kept = i > 0 && slo[i - 1] < C;
-    if (kept && ranks[i + 1] != ranks[i]) starts[ranks[i]] = (uint32_t)i;
-    if (!kept && (i == 0 || prev_kept)) starts[R] = (uint32_t)i;
-    if (i == 0) count[0] = (int64_t)R;
-  }
-}
-
-// One lane per run; a run longer than LONG_RUN is taken by the whole wave afterwards.
+// The runs of equal (lo, hi) among the kept edges come from csrc/sorted_runs.hpp: lo is the major
+// word, hi the minor one, C the limit that sends the dropped edges to the tail.  keys.major is
+// lo in sorted order, keys.minor[keys.order[i]] the hi of sorted position i; starts [R + 1] ends
+// with the number of kept edges.  One lane per run; a run longer than LONG_RUN is taken by the
+// whole wave afterwards.  *count = R.
 __global__ __launch_bounds__(THREADS) void run_reduce_kernel(
-    const uint32_t* __restrict__ slo, const uint32_t* __restrict__ shi,
-    const uint32_t* __restrict__ perm, const uint32_t* __restrict__ starts,
-    const uint32_t* __restrict__ ranks, int64_t E, const float* __restrict__ w, int reduce,
-    int64_t* __restrict__ out_edges, int64_t out_stride, float* __restrict__ out_w) {
+    SortedKeys keys, const int32_t* __restrict__ starts, const uint32_t* __restrict__ num_runs,
+    const float* __restrict__ w, int reduce, int64_t* __restrict__ out_edges, int64_t out_stride,
+    float* __restrict__ out_w, int64_t* __restrict__ count) {
+  const uint32_t* __restrict__ perm = keys.order;
   const int lane = threadIdx.x & 63;
-  const int64_t R = ranks[E];
+  const int64_t R = *num_runs;
+  if (blockIdx.x == 0 && threadIdx.x == 0) count[0] = R;
   const int64_t step = (int64_t)gridDim.x * blockDim.x;
   for (int64_t base = (int64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63); base < R;
        base += step) {                                        // wave-uniform trip count
@@ -141,8 +106,8 @@ __global__ __launch_bounds__(THREADS) void run_reduce_kernel(
     if (r < R) {
       b = starts[r];
       e = starts[r + 1];
-      out_edges[r] = (int64_t)slo[b];
-      out_edges[out_stride + r] = (int64_t)shi[b];
+      out_edges[r] = (int64_t)keys.major[b];
+      out_edges[out_stride + r] = (int64_t)keys.minor[perm[b]];
     }
     const bool longrun = e - b > LONG_RUN;
     if (r < R && !longrun) {
@@ -167,29 +132,9 @@ __global__ __launch_bounds__(THREADS) void run_reduce_kernel(
   }
 }
 
-struct GraphPlan {
-  size_t off_klo, off_khi, off_glo, off_p1, off_p2, off_flags, off_part, off_sort, total;
-  int64_t part_cap;
-};
-
-static GraphPlan graph_plan(int64_t E) {
-  GraphPlan p;
-  const size_t nb = align_up((size_t)(E > 0 ? E : 1) * 4, 256);
-  size_t o = 0;
-  p.off_klo = o; o += align_up((size_t)(E + 1) * 4, 256);    // later: starts [R + 1]
-  p.off_khi = o; o += nb;
-  p.off_glo = o; o += nb;                                     // later: shi
-  p.off_p1 = o;  o += nb;
-  p.off_p2 = o;  o += nb;
-  const ScanPlan sp = scan_plan(E + 1);
-  p.off_flags = o;
-  p.off_part = o + sp.off_part;
-  p.part_cap = sp.part_cap;
-  o += align_up(sp.total, 256);
-  p.off_sort = o; o += RadixScratch::bytes(E);
-  p.total = o;
-  return p;
-}
+// The whole scratch is the shared plan; its size does not depend on the bits, which the entry
+// knows only with C (the run starts lie over the unsorted lo word there).
+static RunsPlan graph_plan(int64_t E, int bits) { return runs_plan(E, bits, bits, true); }
 
 // ---- round -----------------------------------------------------------------------------------
 __global__ __launch_bounds__(THREADS) void means_kernel(
@@ -416,7 +361,7 @@ using namespace spt::merge;
 
 extern "C" size_t spt_component_graph_workspace_bytes(int64_t num_edges) {
   if (num_edges < 0) return 0;
-  return graph_plan(num_edges).total;
+  return graph_plan(num_edges, 1).total;
 }
 
 extern "C" int spt_component_graph_f32(const int64_t* edge_index, int64_t num_edges,
@@ -437,38 +382,18 @@ extern "C" int spt_component_graph_f32(const int64_t* edge_index, int64_t num_ed
   (void)hipMemsetAsync(counts, 0, 2 * 8, stream);
   if (E == 0) return 0;
   SPT_CHECK_ARG(edge_index && out_edges && out_attr, "null pointer");
-  const GraphPlan p = graph_plan(E);
+  const RunsPlan p = graph_plan(E, bits_for(C + 1));
   SPT_CHECK_ARG(ws && ws_bytes >= p.total, "workspace too small");
   char* base = (char*)ws;
-  uint32_t* klo = (uint32_t*)(base + p.off_klo);
-  uint32_t* khi = (uint32_t*)(base + p.off_khi);
-  uint32_t* glo = (uint32_t*)(base + p.off_glo);
-  uint32_t* p1 = (uint32_t*)(base + p.off_p1);
-  uint32_t* p2 = (uint32_t*)(base + p.off_p2);
-  uint32_t* flags = (uint32_t*)(base + p.off_flags);
-  uint32_t* part = (uint32_t*)(base + p.off_part);
-  RadixScratch s;
-  s.carve(base + p.off_sort, E);
+  Runs r = runs_carve(base, p, E);
 
   const int g = stream_grid(E + 1, THREADS);
-  key_kernel<<<g, THREADS, 0, stream>>>(edge_index, E, edge_stride, index, num_nodes, C, klo, khi,
-                                        counts + 1);
-  // least significant half first: by hi, then (stable) by lo
-  const int bits = bits_for(C + 1);
-  const uint32_t *ks, *vs, *slo;
-  SPT_CHECK_ARG(radix_sort_pairs<2>(nullptr, khi, nullptr, E, bits, s, p1, &ks, &vs, stream) == 0,
+  key_kernel<<<g, THREADS, 0, stream>>>(edge_index, E, edge_stride, index, num_nodes, C,
+                                        r.in.major, r.in.minor, counts + 1);
+  SPT_CHECK_ARG(find_runs(base, p, r, E, (uint64_t)C, stream) == 0,
                 "scan partials do not fit their region");
-  gather_u32_kernel<<<g, THREADS, 0, stream>>>(klo, p1, E, glo);
-  SPT_CHECK_ARG(radix_sort_pairs<0>(nullptr, glo, p1, E, bits, s, p2, &slo, &vs, stream) == 0,
-                "scan partials do not fit their region");
-  uint32_t* shi = glo;                                        // the sort has read glo
-  heads_kernel<<<g, THREADS, 0, stream>>>(slo, khi, p2, E, (uint32_t)C, shi, flags);
-  SPT_CHECK_ARG(device_exclusive_scan(flags, E + 1, part, p.part_cap, stream) == 0,
-                "scan partials do not fit their region");
-  uint32_t* starts = klo;                                     // the gather has read klo
-  starts_kernel<<<g, THREADS, 0, stream>>>(slo, flags, E, (uint32_t)C, starts, counts);
-  run_reduce_kernel<<<g, THREADS, 0, stream>>>(slo, shi, p2, starts, flags, E, edge_attr, reduce,
-                                               out_edges, out_stride, out_attr);
+  run_reduce_kernel<<<g, THREADS, 0, stream>>>(r.sorted, r.run_start, r.num_runs, edge_attr,
+                                               reduce, out_edges, out_stride, out_attr, counts);
   SPT_CHECK_LAUNCH();
   return 0;
 }

@@ -4,8 +4,8 @@
 // the instances' semantic logits; and, for the panoptic criterion, the major object of every
 // cluster (InstanceData.major) with its data-dependent branch kept on the device.
 //
-// Grouping is always ONE stable radix sort of a key as wide as its extents need (low word, then
-// high word, as csrc/voxel.hip), run heads through the device scan, and integer run sums: no
+// Grouping is always ONE stable radix sort of a key as wide as its extents need and the runs of
+// equal keys (csrc/sorted_runs.hpp), and integer run sums: no
 // float and no atomic whose order matters takes part in an integer result.  `/` is the correctly
 // rounded IEEE division (no fast-math flag on this file, no reciprocal) and (float)int64 rounds
 // to nearest even, as torch converts.
@@ -15,7 +15,7 @@
 // loop runs over them; parents, labels and predictions are range-checked before they index a
 // table; sorted positions and run starts are this file's own scratch and are checked all the same.
 #include "common.hpp"
-#include "radix_sort.hpp"
+#include "sorted_runs.hpp"
 
 #include <algorithm>
 #include <limits.h>
@@ -159,48 +159,6 @@ __global__ __launch_bounds__(THREADS) void merge_keys_kernel(
     lo32[j] = (uint32_t)key;
     if (hi32) hi32[j] = (uint32_t)(key >> 32);
     pair_parent[j] = (int32_t)par;
-  }
-}
-
-__global__ void gather_u32_kernel(const uint32_t* __restrict__ src,
-                                  const uint32_t* __restrict__ perm, int64_t n,
-                                  uint32_t* __restrict__ out) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-    out[i] = src[perm[i]];
-}
-
-__device__ __forceinline__ uint64_t sorted_key(const uint32_t* __restrict__ ks,
-                                               const uint32_t* __restrict__ lo32,
-                                               const uint32_t* __restrict__ order32, int64_t i,
-                                               bool two) {
-  if (!two) return ks[i];
-  return ((uint64_t)ks[i] << 32) | lo32[order32[i]];
-}
-
-// flag[i] = 1 where a run starts, flag[n] = 0: after the exclusive scan flag[i + 1] - 1 is the
-// run of sorted position i and flag[n] the number of runs
-__global__ void heads_kernel(const uint32_t* __restrict__ ks, const uint32_t* __restrict__ lo32,
-                             const uint32_t* __restrict__ order32, int64_t n, int two,
-                             uint32_t* __restrict__ flag) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= n; i += stride) {
-    uint32_t f = 0;
-    if (i < n)
-      f = (i == 0) || sorted_key(ks, lo32, order32, i, two) !=
-                          sorted_key(ks, lo32, order32, i - 1, two);
-    flag[i] = f;
-  }
-}
-
-// run_start[r] = first sorted position of run r, run_start[R] = n
-__global__ void starts_kernel(const uint32_t* __restrict__ excl, int64_t n,
-                              int32_t* __restrict__ run_start) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const uint32_t before = excl[i], upto = excl[i + 1];       // heads in [0, i) and in [0, i]
-    if (upto != before) run_start[upto - 1] = (int32_t)i;      // 0 <= upto - 1 <= i < n
-    if (i == n - 1) run_start[upto] = (int32_t)n;              // upto <= n
   }
 }
 
@@ -660,82 +618,14 @@ MajorPlan major_plan(int64_t G) {
   return m;
 }
 
-// ---- scratch of "sort n keys of key_bits bits, find the runs" ------------------------------------
-struct RunsPlan {
-  size_t off_lo, off_order, off_hi, off_hig, off_perm, off_sort, off_scan, off_start, total;
-  ScanPlan scan;
-};
-
-RunsPlan runs_plan(int64_t n, int key_bits) {
-  RunsPlan p;
-  const size_t nb = align_up((size_t)(n > 0 ? n : 1) * 4, 256);
-  const bool two = key_bits > 32;
-  size_t off = 0;
-  p.off_lo = off; off += nb;
-  p.off_order = off; off += nb;
-  p.off_hi = off; off += two ? nb : 0;
-  p.off_hig = off; off += two ? nb : 0;
-  p.off_perm = off; off += two ? nb : 0;
-  p.off_sort = off; off += RadixScratch::bytes(n);
-  p.scan = scan_plan(n + 1);
-  p.off_scan = off; off += p.scan.total;
-  p.off_start = off; off += align_up((size_t)(n + 1) * 4, 256);
-  p.total = off;
-  return p;
-}
-
-struct Runs {
-  uint32_t *lo32, *hi32, *order32, *excl;
-  int32_t* run_start;
-  const uint32_t* num_runs;
-};
-
-Runs runs_carve(char* base, const RunsPlan& p, int64_t n, int key_bits) {
-  Runs r;
-  r.lo32 = (uint32_t*)(base + p.off_lo);
-  r.order32 = (uint32_t*)(base + p.off_order);
-  r.hi32 = key_bits > 32 ? (uint32_t*)(base + p.off_hi) : nullptr;
-  r.excl = (uint32_t*)(base + p.off_scan);
-  r.run_start = (int32_t*)(base + p.off_start);
-  r.num_runs = r.excl + n;
-  return r;
-}
-
-// lo32 / hi32 hold the keys: stable sort, heads, scan, run starts.  0, or -1 when a scratch
-// region is too small (nothing of the failing step is launched).
-int find_runs(char* base, const RunsPlan& p, const Runs& r, int64_t n, int key_bits,
-              hipStream_t stream) {
-  const bool two = key_bits > 32;
-  RadixScratch s;
-  s.carve(base + p.off_sort, n);
-  const int g = stream_grid(n, THREADS);
-  const uint32_t *ks = nullptr, *vs = nullptr;
-  if (!two) {
-    if (radix_sort_pairs<2>(nullptr, r.lo32, nullptr, n, key_bits, s, r.order32, &ks, &vs, stream))
-      return -1;
-  } else {
-    uint32_t* hig = (uint32_t*)(base + p.off_hig);
-    uint32_t* perm = (uint32_t*)(base + p.off_perm);
-    if (radix_sort_pairs<2>(nullptr, r.lo32, nullptr, n, 32, s, perm, &ks, &vs, stream)) return -1;
-    gather_u32_kernel<<<g, THREADS, 0, stream>>>(r.hi32, perm, n, hig);
-    if (radix_sort_pairs<0>(nullptr, hig, perm, n, key_bits - 32, s, r.order32, &ks, &vs, stream))
-      return -1;
-  }
-  heads_kernel<<<stream_grid(n + 1, THREADS), THREADS, 0, stream>>>(ks, r.lo32, r.order32, n, two,
-                                                                     r.excl);
-  uint32_t* part = (uint32_t*)(base + p.off_scan + p.scan.off_part);
-  if (device_exclusive_scan(r.excl, n + 1, part, p.scan.part_cap, stream)) return -1;
-  starts_kernel<<<g, THREADS, 0, stream>>>(r.excl, n, r.run_start);
-  return 0;
-}
-
+// ---- the entries' scratch: sort + runs (csrc/sorted_runs.hpp), then their own regions -------------
 struct MergePlan {
   RunsPlan runs;
   size_t off_parent, total;
 };
 MergePlan merge_plan(int64_t P, int key_bits) {
   MergePlan m;
-  m.runs = runs_plan(P, key_bits);
+  m.runs = runs_plan(P, key_bits, true);
   m.off_parent = m.runs.total;
   m.total = m.off_parent + align_up((size_t)(P > 0 ? P : 1) * 4, 256);
   return m;
@@ -747,7 +637,7 @@ struct StatsPlan {
 };
 StatsPlan stats_plan(int64_t P, int64_t G, int key_bits) {
   StatsPlan m;
-  m.runs = runs_plan(P, key_bits);
+  m.runs = runs_plan(P, key_bits, true);
   size_t off = m.runs.total;
   m.off_cluster = off; off += align_up((size_t)(P > 0 ? P : 1) * 4, 256);
   m.off_size = off; off += align_up((size_t)(G > 0 ? G : 1) * 8, 256);
@@ -812,15 +702,17 @@ extern "C" int spt_merge_instances_i64(const int64_t* pointers, const int64_t* o
   const MergePlan m = merge_plan(P, key_bits);
   SPT_CHECK_ARG(ws && ws_bytes >= m.total, "workspace too small");
   char* base = (char*)ws;
-  const Runs r = runs_carve(base, m.runs, P, key_bits);
+  Runs r = runs_carve(base, m.runs, P);
   int32_t* pair_parent = (int32_t*)(base + m.off_parent);
   const int g = stream_grid(P, THREADS);
   merge_keys_kernel<<<g, THREADS, 0, stream>>>(pointers, obj, idx, G, P, num_parents, obj_lo,
-                                               obj_bits, r.lo32, r.hi32, pair_parent, record);
-  SPT_CHECK_ARG(find_runs(base, m.runs, r, P, key_bits, stream) == 0, "sort scratch too small");
-  merge_runs_kernel<<<g, THREADS, 0, stream>>>(obj, count, y, r.order32, r.run_start, r.num_runs,
-                                               pair_parent, P, num_parents, out_pointers, out_obj,
-                                               out_count, out_y, record);
+                                               obj_bits, r.in.minor, r.in.major, pair_parent,
+                                               record);
+  SPT_CHECK_ARG(find_runs(base, m.runs, r, P, NO_MAJOR_LIMIT, stream) == 0,
+                "sort scratch too small");
+  merge_runs_kernel<<<g, THREADS, 0, stream>>>(obj, count, y, r.sorted.order, r.run_start,
+                                               r.num_runs, pair_parent, P, num_parents,
+                                               out_pointers, out_obj, out_count, out_y, record);
   SPT_CHECK_LAUNCH();
   return 0;
 }
@@ -847,7 +739,7 @@ extern "C" int spt_pair_stats_i64(const int64_t* pointers, const int64_t* obj,
   const StatsPlan m = stats_plan(P, G, obj_bits);
   SPT_CHECK_ARG(ws && ws_bytes >= m.total, "workspace too small");
   char* base = (char*)ws;
-  const Runs r = runs_carve(base, m.runs, P, obj_bits);
+  Runs r = runs_carve(base, m.runs, P);
   int32_t* pair_cluster = (int32_t*)(base + m.off_cluster);
   int64_t* cl_size = (int64_t*)(base + m.off_size);
   int64_t* cl_void = (int64_t*)(base + m.off_void);
@@ -855,10 +747,11 @@ extern "C" int spt_pair_stats_i64(const int64_t* pointers, const int64_t* obj,
   cluster_sizes_kernel<<<stream_grid(G, THREADS), THREADS, 0, stream>>>(
       pointers, count, y, G, P, C, cl_size, cl_void, cluster_void, status);
   stats_keys_kernel<<<g, THREADS, 0, stream>>>(pointers, obj, y, G, P, C, obj_lo, obj_bits,
-                                               cl_size, cluster_void, r.lo32, r.hi32,
+                                               cl_size, cluster_void, r.in.minor, r.in.major,
                                                pair_cluster, a_size, pair_void, status);
-  SPT_CHECK_ARG(find_runs(base, m.runs, r, P, obj_bits, stream) == 0, "sort scratch too small");
-  object_runs_kernel<<<g, THREADS, 0, stream>>>(count, cropped_in, r.order32, r.run_start,
+  SPT_CHECK_ARG(find_runs(base, m.runs, r, P, NO_MAJOR_LIMIT, stream) == 0,
+                "sort scratch too small");
+  object_runs_kernel<<<g, THREADS, 0, stream>>>(count, cropped_in, r.sorted.order, r.run_start,
                                                 r.num_runs, pair_cluster, cl_size, cl_void,
                                                 cluster_void, pair_void, a_size, P, G, b_size, iou,
                                                 pair_cropped, kept_iou, gt_head);

@@ -2,7 +2,7 @@
 //
 // Kernel map: (batch, z, y, x) keys with every axis range padded by r*d (a neighbour position
 // outside the cloud's bounds has a key of its own that no voxel holds, so it is absent and never
-// aliases), sorted once by the radix sort of radix_sort.hpp; per voxel and per (dz, dy) row one
+// aliases), sorted once by the wide-key sort of sorted_runs.hpp; per voxel and per (dz, dy) row one
 // binary search and a short walk along x.  Two passes over the same searches - count, then fill -
 // around one exclusive scan give the pairs as CSR by output voxel: rowptr [N + 1], and per pair
 // the neighbour, the offset index (ascending inside a voxel) and the output voxel.
@@ -18,7 +18,7 @@
 // over the pairs of offset o, listed in ascending pair order by one stable sort of the offsets:
 // DW_CHUNKS fixed chunks per offset, one wave each, then a post pass adds the chunks in a fixed
 // tree.  dbias: DB_PARTS fixed row ranges, then the same post pass.  No float atomics anywhere.
-#include "radix_sort.hpp"
+#include "sorted_runs.hpp"
 
 namespace spt {
 namespace {
@@ -105,23 +105,12 @@ __global__ __launch_bounds__(THREADS) void keys_kernel(const int32_t* __restrict
   }
 }
 
-__global__ void gather_u32_kernel(const uint32_t* __restrict__ src,
-                                  const uint32_t* __restrict__ perm, int64_t n,
-                                  uint32_t* __restrict__ out) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-    out[i] = src[perm[i]];
-}
-
-__global__ void sorted_keys_kernel(const uint32_t* __restrict__ ks,
-                                   const uint32_t* __restrict__ lo32,
-                                   const uint32_t* __restrict__ order32, int64_t n, int two,
-                                   uint64_t* __restrict__ skeys, int32_t* __restrict__ sorder) {
+__global__ void sorted_keys_kernel(SortedKeys keys, int64_t n, uint64_t* __restrict__ skeys,
+                                   int32_t* __restrict__ sorder) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += stride) {
-    const uint32_t p = order32[t];
-    skeys[t] = two ? (((uint64_t)ks[t] << 32) | lo32[p]) : (uint64_t)ks[t];
-    sorder[t] = (int32_t)p;
+    skeys[t] = sorted_key(keys, t);
+    sorder[t] = (int32_t)keys.order[t];
   }
 }
 
@@ -364,22 +353,19 @@ __global__ __launch_bounds__(64) void conv_dbias_kernel(const float* __restrict_
   partial[(size_t)blockIdx.x * co + col] = s;
 }
 
+// the sort (csrc/sorted_runs.hpp), the permutation it borrows for a key of two words, and the
+// partials of the scan over rowptr
 struct CountPlan {
-  size_t off_lo, off_order, off_hi, off_hig, off_perm, off_sort, off_part, total;
+  SortPlan sort;
+  size_t off_perm, off_part, total;
   int64_t part_cap;
 };
 
 CountPlan count_plan(int64_t n, int key_bits) {
   CountPlan p;
-  const size_t nb = align_up((size_t)(n > 0 ? n : 1) * 4, 256);
-  const bool two = key_bits > 32;
-  size_t off = 0;
-  p.off_lo = off; off += nb;
-  p.off_order = off; off += nb;
-  p.off_hi = off; off += two ? nb : 0;
-  p.off_hig = off; off += two ? nb : 0;
-  p.off_perm = off; off += two ? nb : 0;
-  p.off_sort = off; off += RadixScratch::bytes(n);
+  p.sort = sort_plan(n, key_bits);
+  size_t off = p.sort.total;
+  p.off_perm = off; off += key_bits > 32 ? align_up((size_t)n * 4, 256) : 0;
   p.off_part = off; off += scan_part_bytes(n + 1);
   p.part_cap = (int64_t)(scan_part_bytes(n + 1) / 4);
   p.total = off;
@@ -446,33 +432,18 @@ extern "C" int spt_sparse_map_count(const int32_t* coords, const int64_t* batch,
                 "the key fields must add up to 1 .. 63 bits (batch bits only with a batch)");
   const CountPlan p = count_plan(n, key_bits);
   SPT_CHECK_ARG(ws && ws_bytes >= p.total, "workspace too small");
-  const bool two = key_bits > 32;
   char* base = (char*)ws;
-  uint32_t* lo32 = (uint32_t*)(base + p.off_lo);
-  uint32_t* order32 = (uint32_t*)(base + p.off_order);
-  uint32_t* hi32 = two ? (uint32_t*)(base + p.off_hi) : nullptr;
-  uint32_t* hig = two ? (uint32_t*)(base + p.off_hig) : nullptr;
-  uint32_t* perm = two ? (uint32_t*)(base + p.off_perm) : nullptr;
-  RadixScratch s;
-  s.carve(base + p.off_sort, n);
+  const WideKeys keys = sort_carve(base, p.sort);
+  uint32_t* perm = (uint32_t*)(base + p.off_perm);
   uint32_t* part = (uint32_t*)(base + p.off_part);
 
   SPT_CHECK_ARG(hipMemsetAsync(record, 0, 2 * sizeof(int64_t), stream) == hipSuccess,
                 "could not queue the record reset");
   const int g = stream_grid(n, THREADS);
-  keys_kernel<<<g, THREADS, 0, stream>>>(coords, batch, n, G, lo32, hi32);
-  const uint32_t *ks = nullptr, *vs = nullptr;
-  if (!two) {
-    SPT_CHECK_ARG(radix_sort_pairs<2>(nullptr, lo32, nullptr, n, key_bits, s, order32, &ks, &vs,
-                                      stream) == 0, "sort scratch too small");
-  } else {
-    SPT_CHECK_ARG(radix_sort_pairs<2>(nullptr, lo32, nullptr, n, 32, s, perm, &ks, &vs,
-                                      stream) == 0, "sort scratch too small");
-    gather_u32_kernel<<<g, THREADS, 0, stream>>>(hi32, perm, n, hig);
-    SPT_CHECK_ARG(radix_sort_pairs<0>(nullptr, hig, perm, n, key_bits - 32, s, order32, &ks, &vs,
-                                      stream) == 0, "sort scratch too small");
-  }
-  sorted_keys_kernel<<<g, THREADS, 0, stream>>>(ks, lo32, order32, n, two, skeys, sorder);
+  keys_kernel<<<g, THREADS, 0, stream>>>(coords, batch, n, G, keys.minor, keys.major);
+  SortedKeys sorted;
+  SPT_CHECK_ARG(sort_wide(base, p.sort, n, perm, stream, &sorted) == 0, "sort scratch too small");
+  sorted_keys_kernel<<<g, THREADS, 0, stream>>>(sorted, n, skeys, sorder);
   map_rows_kernel<false><<<g, THREADS, 0, stream>>>(coords, batch, n, G, skeys, sorder,
                                                     (uint32_t*)rowptr, nullptr, nullptr, nullptr,
                                                     nullptr, (unsigned long long*)record);

@@ -9,8 +9,8 @@
 // labels are range-checked before they index a row.  Every index into an output is a sorted
 // position (< n) or a voxel id (< V <= n).
 #include "common.hpp"
-#include "radix_sort.hpp"
 #include "rng.hpp"
+#include "sorted_runs.hpp"
 
 #include <limits.h>
 
@@ -155,55 +155,23 @@ __global__ __launch_bounds__(THREADS) void keys_kernel(
   }
 }
 
-__global__ void gather_u32_kernel(const uint32_t* __restrict__ src,
-                                  const uint32_t* __restrict__ perm, int64_t n,
-                                  uint32_t* __restrict__ out) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-    out[i] = src[perm[i]];
-}
-
-// key of sorted position i: one word - the sorted keys themselves; two words - the sorted high
-// word and the low word of the point (the second sort carried the points, not the low words)
-__device__ __forceinline__ uint64_t sorted_key(const uint32_t* __restrict__ ks,
-                                               const uint32_t* __restrict__ lo32,
-                                               const uint32_t* __restrict__ order32, int64_t i,
-                                               bool two) {
-  if (!two) return ks[i];
-  return ((uint64_t)ks[i] << 32) | lo32[order32[i]];
-}
-
-// flag[i] = 1 where a run starts, flag[n] = 0: after the exclusive scan flag[i + 1] - 1 is the
-// voxel of sorted position i and flag[n] = V
-__global__ void heads_kernel(const uint32_t* __restrict__ ks, const uint32_t* __restrict__ lo32,
-                             const uint32_t* __restrict__ order32, int64_t n, int two,
-                             uint32_t* __restrict__ flag) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= n; i += stride) {
-    uint32_t f = 0;
-    if (i < n)
-      f = (i == 0) || sorted_key(ks, lo32, order32, i, two) !=
-                          sorted_key(ks, lo32, order32, i - 1, two);
-    flag[i] = f;
-  }
-}
-
-__global__ void groups_kernel(const uint32_t* __restrict__ ks, const uint32_t* __restrict__ lo32,
-                              const uint32_t* __restrict__ order32,
-                              const uint32_t* __restrict__ excl, int64_t n, int two, KeyLayout L,
-                              int64_t* __restrict__ pointers, int64_t* __restrict__ cluster,
-                              int64_t* __restrict__ order, int64_t* __restrict__ last,
-                              int32_t* __restrict__ coords, int64_t* __restrict__ count) {
+// excl: the scanned run flags of csrc/sorted_runs.hpp - excl[i + 1] - 1 is the voxel of sorted
+// position i and excl[n] = V
+__global__ void groups_kernel(SortedKeys keys, const uint32_t* __restrict__ excl, int64_t n,
+                              KeyLayout L, int64_t* __restrict__ pointers,
+                              int64_t* __restrict__ cluster, int64_t* __restrict__ order,
+                              int64_t* __restrict__ last, int32_t* __restrict__ coords,
+                              int64_t* __restrict__ count) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     const uint32_t before = excl[i], upto = excl[i + 1];       // heads in [0, i) and in [0, i]
     const int64_t v = (int64_t)upto - 1;                       // 0 <= v < V <= n
-    const int64_t p = order32[i];
+    const int64_t p = keys.order[i];
     order[i] = p;
     cluster[p] = v;
     if (upto != before) {                                      // a run starts here
       pointers[v] = i;
-      const uint64_t key = sorted_key(ks, lo32, order32, i, two);
+      const uint64_t key = sorted_key(keys, i);
       int shift = 0;
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
@@ -415,28 +383,6 @@ __global__ __launch_bounds__(THREADS) void last_kernel(
   }
 }
 
-struct GroupsPlan {
-  size_t off_lo, off_hi, off_hig, off_perm, off_order, off_sort, off_scan, total;
-  ScanPlan scan;
-};
-
-GroupsPlan groups_plan(int64_t n, int key_bits) {
-  GroupsPlan p;
-  const size_t nb = align_up((size_t)(n > 0 ? n : 1) * 4, 256);
-  const bool two = key_bits > 32;
-  size_t off = 0;
-  p.off_lo = off; off += nb;
-  p.off_order = off; off += nb;
-  p.off_hi = off; off += two ? nb : 0;
-  p.off_hig = off; off += two ? nb : 0;
-  p.off_perm = off; off += two ? nb : 0;
-  p.off_sort = off; off += RadixScratch::bytes(n);
-  p.scan = scan_plan(n + 1);
-  p.off_scan = off; off += p.scan.total;
-  p.total = off;
-  return p;
-}
-
 }  // namespace
 }  // namespace spt
 
@@ -458,7 +404,7 @@ extern "C" int spt_voxel_bounds_f32(const float* pos, int64_t n, int64_t ld, flo
 
 extern "C" size_t spt_voxel_groups_workspace_bytes(int64_t n, int key_bits) {
   if (!count_ok(n) || n < 1 || key_bits < 1 || key_bits > 63) return 0;
-  return groups_plan(n, key_bits).total;
+  return runs_plan(n, key_bits, false).total;
 }
 
 extern "C" int spt_voxel_groups_f32(const float* pos, int64_t n, int64_t ld, float size,
@@ -482,39 +428,17 @@ extern "C" int spt_voxel_groups_f32(const float* pos, int64_t n, int64_t ld, flo
   }
   SPT_CHECK_ARG(batch || bits[3] == 0, "batch bits without a batch");
   SPT_CHECK_ARG(key_bits >= 1 && key_bits <= 63, "the key needs 1 .. 63 bits");
-  const GroupsPlan p = groups_plan(n, key_bits);
+  const RunsPlan p = runs_plan(n, key_bits, false);
   SPT_CHECK_ARG(ws && ws_bytes >= p.total, "workspace too small");
-  const bool two = key_bits > 32;
   char* base = (char*)ws;
-  uint32_t* lo32 = (uint32_t*)(base + p.off_lo);
-  uint32_t* order32 = (uint32_t*)(base + p.off_order);
-  uint32_t* hi32 = two ? (uint32_t*)(base + p.off_hi) : nullptr;
-  uint32_t* hig = two ? (uint32_t*)(base + p.off_hig) : nullptr;
-  uint32_t* perm = two ? (uint32_t*)(base + p.off_perm) : nullptr;
-  RadixScratch s;
-  s.carve(base + p.off_sort, n);
-  uint32_t* flag = (uint32_t*)(base + p.off_scan);
-  uint32_t* part = (uint32_t*)(base + p.off_scan + p.scan.off_part);
+  Runs r = runs_carve(base, p, n);
 
   const int g = stream_grid(n, THREADS);
-  keys_kernel<<<g, THREADS, 0, stream>>>(pos, n, ld, size, batch, L, lo32, hi32);
-  const uint32_t *ks = nullptr, *vs = nullptr;
-  if (!two) {
-    SPT_CHECK_ARG(radix_sort_pairs<2>(nullptr, lo32, nullptr, n, key_bits, s, order32, &ks, &vs,
-                                      stream) == 0, "sort scratch too small");
-  } else {
-    SPT_CHECK_ARG(radix_sort_pairs<2>(nullptr, lo32, nullptr, n, 32, s, perm, &ks, &vs,
-                                      stream) == 0, "sort scratch too small");
-    gather_u32_kernel<<<g, THREADS, 0, stream>>>(hi32, perm, n, hig);
-    SPT_CHECK_ARG(radix_sort_pairs<0>(nullptr, hig, perm, n, key_bits - 32, s, order32, &ks, &vs,
-                                      stream) == 0, "sort scratch too small");
-  }
-  heads_kernel<<<stream_grid(n + 1, THREADS), THREADS, 0, stream>>>(ks, lo32, order32, n, two,
-                                                                     flag);
-  SPT_CHECK_ARG(device_exclusive_scan(flag, n + 1, part, p.scan.part_cap, stream) == 0,
-                "scan partials too small");
-  groups_kernel<<<g, THREADS, 0, stream>>>(ks, lo32, order32, flag, n, two, L, pointers, cluster,
-                                           order, last, coords, count);
+  keys_kernel<<<g, THREADS, 0, stream>>>(pos, n, ld, size, batch, L, r.in.minor, r.in.major);
+  SPT_CHECK_ARG(sort_runs(base, p, r, n, stream) == 0, "sort scratch too small");
+  SPT_CHECK_ARG(flag_runs(base, p, r, n, NO_MAJOR_LIMIT, stream) == 0, "scan partials too small");
+  groups_kernel<<<g, THREADS, 0, stream>>>(r.sorted, r.excl, n, L, pointers, cluster, order, last,
+                                           coords, count);
   SPT_CHECK_LAUNCH();
   return 0;
 }

@@ -94,6 +94,33 @@ def test_every_reduce_on_duplicates(reduce, dev):
     both(dev, x, pos, ei, w, 4, reduce=reduce)
 
 
+@pytest.mark.parametrize("E,loops", [(4095, 37), (4096, 5), (4097, 1)])
+def test_component_graph_at_the_sort_tile_seam(E, loops, dev):
+    """E around the 4096 keys of one sort tile, 50 components under a relabelling of 200 nodes:
+    duplicates in both directions, and `loops` edges that the relabelling turns into self loops -
+    the rejected tail of the sorted keys, which starts at position 4096 for E = 4097.  Against
+    the package's CPU route, every reduce, bit for bit (both reduce a run in input order)."""
+    from superpoint_transformer_amd import partition as P
+    rng = np.random.default_rng(E)
+    C, n = 50, 200
+    index = (np.arange(n) % C).astype(np.int64)
+    a = rng.integers(0, C, E)
+    b = (a + rng.integers(1, C, E)) % C                              # another component
+    b[:loops] = a[:loops]                                            # the same one: dropped
+    ei = np.stack([a + C * rng.integers(0, n // C, E), b + C * rng.integers(0, n // C, E)])
+    ei = ei[:, rng.permutation(E)].astype(np.int64)
+    w = rng.uniform(0.5, 1.5, E).astype(np.float32)
+    kept = int((index[ei[0]] != index[ei[1]]).sum())
+    assert kept == E - loops and 0 < loops
+    for reduce in ("add", "mean", "max", "min", "mul"):
+        wE, wW = P.component_graph(_t(index, "cpu"), _t(ei, "cpu"), _t(w, "cpu"), reduce,
+                                   num_components=C)
+        gE, gW = P.component_graph(_t(index, dev), _t(ei, dev), _t(w, dev), reduce, num_components=C)
+        assert gE.is_cuda and wE.shape[1] < kept                     # duplicates were merged
+        assert torch.equal(gE.cpu(), wE), reduce
+        assert torch.equal(gW.cpu().view(torch.int32), wW.view(torch.int32)), reduce
+
+
 def test_merge_only_small_and_one_iteration(dev):
     x, pos, ei = R.grid_case(24, 0.3, D=2, seed=1)
     both(dev, x, pos, ei, None, 5, merge_only_small=True)

@@ -214,6 +214,32 @@ def test_aliasing_traps(K, d, pow2, dev):
         assert triples == sorted(R.pairs_dense(coords, batch, K, d))
 
 
+def test_map_with_a_key_wider_than_32_bits(dev):
+    """Three 3 x 3 x 3 blocks far apart in two batch items: 14 + 14 + 13 + 1 key bits, so the keys
+    are sorted as two words (csrc/sorted_runs.hpp).  The device map must be the CPU route's, pair
+    for pair - also on a workspace of exactly the promised size between guards, NaN-filled."""
+    from guarded import GuardedArena, exact_workspaces, poisoned_fresh_tensors
+    from superpoint_transformer_amd import sparse as S
+    offsets = torch.tensor([[0, 0, 0], [5000, 5000, 5000], [-5000, 9000, 2000]])
+    coords = torch.cat([R.full_block(3) + o for o in offsets])
+    batch = torch.tensor([0, 1, 1]).repeat_interleave(27)
+    order = torch.randperm(81, generator=torch.Generator().manual_seed(81))
+    coords, batch = coords[order], batch[order]
+    cols = [coords[:, 0], coords[:, 1], coords[:, 2], batch]
+    _, bits, total = S._key_layout([int(v.min()) for v in cols], [int(v.max()) for v in cols], 1)
+    assert total > 32 and max(bits) <= 32, (bits, total)
+    cmap = S.build_kernel_map(coords, batch, 3, 1)
+    assert cmap.num_pairs == 3 * 7 ** 3             # 7 pairs within reach per axis, no block meets another
+    arena = GuardedArena(dev, guard_byte=0xFF, fill_byte=0xFF)
+    with poisoned_fresh_tensors(dev), exact_workspaces(arena):
+        guarded = S.build_kernel_map(coords.to(dev), batch.to(dev), 3, 1)
+    assert len(arena.sizes()) >= 1
+    for kmap in (S.build_kernel_map(coords.to(dev), batch.to(dev), 3, 1), guarded):
+        assert kmap.num_pairs == cmap.num_pairs
+        for name in ("rowptr", "nbr", "off", "row"):
+            assert torch.equal(getattr(kmap, name).cpu(), getattr(cmap, name)), name
+
+
 def test_quantize_point_coordinates_on_the_device(dev):
     from superpoint_transformer_amd import sparse as S
     from superpoint_transformer_amd.data import NAG, Data
