@@ -1468,6 +1468,47 @@ int spt_edge_affinity_loss_bwd_f32(const float* logits, const float* target,
                                    const float* case_weight, const float* pos_weight,
                                    const float* gout, const double* den, float* glogits,
                                    spt_stream_t stream);
+/* Edge-contrast focal loss of the partition training stage (PartitionCriterion with
+ * BinaryFocalLoss, src/loss/partition_criterion.py:92-145, src/loss/focal.py:194-220), without
+ * compacting the edge list and without a host read.  x f32 [N, D] (row stride ldx elements,
+ * 1 <= D <= 128), y int64 label histograms [N, ycols >= C] (columns past C are void) or, with
+ * ycols == 0, int64 labels [N] (outside [0, C): void), edge_index int64 [2, E] in any order.
+ *   label_n = first arg-max of y[n, :C]; a node is void when that maximum is 0.
+ *   An edge (i, j) is dropped if i == j or an end is void; an end outside [0, N) drops it too and
+ *   is counted.  Otherwise t = (label_i == label_j): inter (t = 0) or intra (t = 1).
+ *   ratio < 0: every kept edge is selected.  ratio in (0, 1]: all inter edges and exactly
+ *   n_major = (int) (f32(n_inter) * f32(1 / ratio - 1)) intra edges (clamped to n_intra), those
+ *   with the smallest keys (rand32(s, e) << 32 | e), e the position in the list, s = seed ^
+ *   (rand32(0x5EED, 2 calls) << 32 | rand32(0x5EED, 2 calls + 1)) with (seed, calls) = state[0..1]
+ *   (a DEVICE int64 [2]); the last kernel adds 1 to state[1].
+ *   Per selected edge, in f64: d = |x_i - x_j|, p = exp(-d / T), q = t ? p : 1 - p,
+ *   q' = eps + (1 - 2 eps) q, w = t ? weight : 1 - weight, l = -w (1 - q')^gamma log q'.
+ *   fwd: loss[1] f32 = sum l / n_selected (f64 partial sums per workgroup, added in a fixed
+ *        order), exactly 0 when nothing is selected or there is no inter edge; den[1] f64 =
+ *        n_selected, 0 in that case (the backward's switch).  code uint8 [E] out: 0 not selected,
+ *        1 inter, 2 intra - the backward's input.  counts (may be NULL) int64 [3] = n_inter,
+ *        n_intra, n_selected (written).  status (may be NULL) int32 [2]: [0] += edges with an end
+ *        out of range, [1] |= 1 when n_major was clamped.  selected (may be NULL) uint8 [E] = the
+ *        selection as 0 / 1.  ws: spt_partition_loss_workspace_bytes.
+ *   bwd: gx[n] = gout[0] / den[0] * sum over the selected edges e at n of c_e (x_n - x_other(e)),
+ *        c_e = dl/dd / d (0 at d == 0); one lane group per node walks its run of the by-source
+ *        view, then of the by-target view (spt_csr_build of the two rows of edge_index with ends
+ *        clamped into [0, N)), and writes the row once: no atomics, zero rows for isolated nodes
+ *        and when den[0] == 0.  gout / den are device scalars. */
+size_t spt_partition_loss_workspace_bytes(int64_t N, int64_t E);
+int spt_partition_loss_fwd_f32(const float* x, int64_t ldx, int64_t N, int D, const int64_t* y,
+                               int ycols, int C, const int64_t* edge_index, int64_t E,
+                               double temperature, double gamma, double weight, double epsilon,
+                               double ratio, int64_t* state, float* loss, double* den, uint8_t* code,
+                               int64_t* counts, int32_t* status, uint8_t* selected, void* ws,
+                               size_t ws_bytes, spt_stream_t stream);
+int spt_partition_loss_bwd_f32(const float* x, int64_t ldx, int64_t N, int D,
+                               const int64_t* edge_index, int64_t E, const uint8_t* code,
+                               const int32_t* src_rowptr, const int32_t* src_perm,
+                               const int32_t* tgt_rowptr, const int32_t* tgt_perm,
+                               double temperature, double gamma, double weight, double epsilon,
+                               const float* gout, const double* den, float* gx, int64_t ldg,
+                               spt_stream_t stream);
 /* Confusion matrix from segment-level predictions and label histograms, without flattening them
  * to points (ConfusionMatrix.update, src/metrics/semantic.py:66-107): confmat[t, pred[r]] +=
  * h[r, t] for t < C <= 32 (target int64 [rows, ncols >= C]; columns past C are void), or, with

@@ -291,6 +291,11 @@ SIGNATURES = {
     "spt_edge_affinity_loss_fwd_f32": (_int, [_p, _p, _p, _i64, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _p,
                                               _p, _sz, _p]),
     "spt_edge_affinity_loss_bwd_f32": (_int, [_p, _p, _p, _i64, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _p]),
+    "spt_partition_loss_workspace_bytes": (_sz, [_i64, _i64]),
+    "spt_partition_loss_fwd_f32": (_int, [_p, _i64, _i64, _int, _p, _int, _int, _p, _i64, _f64, _f64, _f64,
+                                          _f64, _f64, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "spt_partition_loss_bwd_f32": (_int, [_p, _i64, _i64, _int, _p, _i64, _p, _p, _p, _p, _p, _f64, _f64,
+                                          _f64, _f64, _p, _p, _p, _i64, _p]),
     "spt_superedge_capacity": (_int, []),
     "spt_superedge_workspace_bytes": (_sz, [_i64]),
     "spt_superedge_classify": (_int, [_p, _i64, _p, _i64, _i64, _p, _p, _p, _sz, _p]),

@@ -169,3 +169,82 @@ class PanopticCriterion(torch.nn.Module):
                                                 stats=stats)
         loss = semantic_loss + self.edge_affinity_loss_lambda * edge_affinity_loss
         return loss, semantic_loss, edge_affinity_loss
+
+
+class BinaryFocalLoss(torch.nn.Module):
+    """The reference's two-class focal loss (src/loss/focal.py:171-220), mean reduction: a holder
+    of ``gamma``, ``weight`` (of the True class) and ``epsilon`` for ``PartitionCriterion``, and -
+    for stand-alone use - callable on probabilities ``p`` [n] of the True label and boolean
+    targets ``y`` [n] with the reference's formula."""
+
+    def __init__(self, gamma=0, weight=0.5, epsilon=1e-6):
+        super().__init__()
+        self.gamma = gamma
+        self.weight = weight
+        self.epsilon = epsilon
+
+    def extra_repr(self):
+        return f"gamma={self.gamma}, weight={self.weight}, epsilon={self.epsilon}"
+
+    def forward(self, p, y):
+        yf = y.float()
+        p = (~y).float() + p * (2 * yf - 1)
+        p = self.epsilon + (1 - 2 * self.epsilon) * p
+        weight = yf * self.weight + (1 - yf) * (1 - self.weight)
+        return (-(1 - p) ** self.gamma * torch.log(p) * weight).mean()
+
+
+class PartitionCriterion(torch.nn.Module):
+    """The criterion of the partition training stage (``PartitionCriterion``,
+    src/loss/partition_criterion.py): ``criterion(partition_output) -> (loss, partition_output)``
+    on ``ops.partition_edge_loss`` - embeddings ``x`` that stay close along the edges inside a
+    label and move apart along those across two labels.  The reference's constructor plus
+    ``seed``; the adaptive sample (``adaptive_sampling_ratio``) is drawn in training mode only, on
+    the device, from the module's ``state`` buffer ``(seed, calls)``.  ``sharding`` is accepted and
+    ignored (nothing here gathers the edges' rows into a tensor that could be too large).
+
+    Only ``BinaryFocalLoss`` is a ``loss_function``: its three numbers go to the kernels.
+
+    Deviation: ``partition_output.n_inter_edge`` is a 0-dim int64 DEVICE tensor (a view of the
+    module's ``counts`` buffer ``n_inter, n_intra, n_selected``, rewritten by every call), not a
+    Python int - nothing waits on the host, so a step with this criterion can be captured into a
+    graph.  ``status``: int32 ``[2]`` buffer, see ``ops.partition_edge_loss``."""
+
+    INTER_EDGE_LABEL = 0
+    INTRA_EDGE_LABEL = 1
+
+    def __init__(self, loss_function=None, affinity_temperature=1, adaptive_sampling_ratio=None,
+                 num_classes=None, sharding=None, seed=0):
+        super().__init__()
+        if loss_function is None:
+            loss_function = BinaryFocalLoss()
+        if not isinstance(loss_function, BinaryFocalLoss):
+            raise ValueError("PartitionCriterion runs BinaryFocalLoss on the device; a "
+                             f"{type(loss_function).__name__} loss function is not supported")
+        if num_classes is None:
+            raise ValueError("num_classes is needed: the last column of the histograms is void")
+        self.loss_function = loss_function
+        self.affinity_temperature = affinity_temperature
+        self.adaptive_sampling_ratio = adaptive_sampling_ratio
+        self.sharding = sharding
+        self.num_classes = int(num_classes)
+        self.register_buffer("state", torch.tensor([int(seed), 0], dtype=torch.int64))
+        self.register_buffer("counts", torch.zeros(3, dtype=torch.int64))
+        self.register_buffer("status", torch.zeros(2, dtype=torch.int32))
+
+    def extra_repr(self):
+        return (f"affinity_temperature={self.affinity_temperature}, "
+                f"adaptive_sampling_ratio={self.adaptive_sampling_ratio}, num_classes={self.num_classes}")
+
+    def forward(self, partition_output, selected=None):
+        if not partition_output.has_target:
+            raise ValueError("the partition criterion needs the labels y of the nodes")
+        ratio = self.adaptive_sampling_ratio if self.training else None
+        f = self.loss_function
+        loss = ops.partition_edge_loss(
+            partition_output.x, partition_output.y, partition_output.edge_index, self.num_classes,
+            temperature=self.affinity_temperature, gamma=f.gamma, weight=f.weight, epsilon=f.epsilon,
+            ratio=ratio, state=self.state if ratio is not None else None, counts=self.counts,
+            status=self.status, selected=selected)
+        partition_output.n_inter_edge = self.counts[0]
+        return loss, partition_output

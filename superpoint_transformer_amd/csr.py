@@ -520,6 +520,30 @@ def _edge_csr_fused(edge_index, num_nodes):
     return ecsr
 
 
+_ATTR_ENDS = "_spt_edge_end_views"
+
+
+def edge_end_views(edge_index, num_nodes):
+    """``(by_source, by_target)``: the :class:`SegmentCSR` views of the two rows of a [2, E]
+    ``edge_index`` over ``num_nodes`` nodes, memoised on the ``edge_index`` object (its rows are
+    fresh tensor objects at every ``edge_index[0]``, so ``csr_of`` could not remember them): a
+    fixed graph is sorted once.  Both sorts are stable, so the edges at a node come in ascending
+    position.  Ends outside ``[0, num_nodes)`` are clamped into it for the sort only - whoever
+    walks the runs decides what such an edge is worth (``ops.partition_edge_loss`` drops it)."""
+    n = max(int(num_nodes), 1)
+    key = (edge_index._version, n, edge_index.data_ptr(), edge_index.shape[1])
+    memo = getattr(edge_index, _ATTR_ENDS, None)
+    if memo is not None and memo[0] == key:
+        return memo[1]
+    ends = edge_index.detach().long().clamp(0, n - 1).contiguous()
+    views = (build_csr(ends[0], n), build_csr(ends[1], n))
+    try:
+        setattr(edge_index, _ATTR_ENDS, (key, views))
+    except Exception:
+        pass
+    return views
+
+
 def forget(*tensors):
     """Drop the memoised CSR views of these index tensors (a new batch would
     carry new tensors; benchmarks reusing one batch call this every step so
@@ -529,8 +553,8 @@ def forget(*tensors):
             continue
         # the CSR views AND the run tables / row ranges ops.graph_runs(_via) / graph_ranges
         # memoise on batch vectors and edge indices: a fresh batch pays their read-backs too
-        for a in (_ATTR, _ATTR_BAD, "_spt_graph_runs", "_spt_graph_runs_via", "_spt_graph_ranges",
-                  "_spt_batch_checked"):
+        for a in (_ATTR, _ATTR_BAD, _ATTR_ENDS, "_spt_graph_runs", "_spt_graph_runs_via", "_spt_graph_ranges",
+                  "_spt_batch_checked", "_spt_num_graphs"):
             if hasattr(t, a):
                 try:
                     delattr(t, a)

@@ -640,6 +640,122 @@ class SPTPanopticStep(SPTTrainStep):
         loss.backward()
         return loss
 
+
+class SPTPartitionStep(SPTTrainStep):
+    """The partition training stage of EZ-SP (``PartitionAndSemanticModule`` with
+    ``training_partition_stage=True``, src/models/semantic.py:1505-1566;
+    configs/model/partition/default_ezsp.yaml): ``forward_first_stage`` of a sparse-CNN
+    ``PointStage`` on one level-0 ``Data`` batch, ``criterion.PartitionCriterion`` on the features
+    along ``data.edge_index``, backward, AdamW (lr 1e-4, weight decay 1e-4).  ``step()``,
+    ``capture()`` and the replay are ``SPTTrainStep``'s.
+
+    ``data``: a ``Data`` on ``dev`` with ``x`` [N, F] (the partition's handcrafted features),
+    integer voxel ``coords``, ``batch`` (optional), the label histograms ``y`` [N, C + 1] and the
+    graph ``edge_index`` (``transforms.KNN`` -> ``AdjacencyGraph`` -> ``RemoveKeys``), plus ``pos``
+    for ``evaluate()``.  The batch is static: its kernel map, its by-source / by-target edge
+    views and its graph count are made once and kept on its tensors, so nothing in a step reads
+    the host and a captured step replays with a fresh sample each time (the criterion's device
+    ``state`` advances inside the graph)."""
+    name = "EZ-SP partition stage: sparse CNN fwd + edge-contrast focal loss + bwd + AdamW"
+
+    def __init__(self, data, dev, criterion, cnn=None, cnn_kernel_size=3, partition=None, seed=0,
+                 lr=1e-4, weight_decay=1e-4):
+        from .criterion import PartitionCriterion
+        from .nn import PointStage
+        if not isinstance(criterion, PartitionCriterion):
+            raise ValueError("SPTPartitionStep trains with a criterion.PartitionCriterion")
+        for key in ("x", "pos", "coords", "y", "edge_index"):
+            if data.get(key) is None:
+                raise ValueError(f"the partition stage needs data.{key}")
+        self.data, self.dev, self.world = data, dev, 1
+        self.n = [data.x.shape[0]]
+        self.net_name, self.workload, self.k_timers = "ezsp-partition", None, None
+        cnn = [data.x.shape[1], 32, 32, 32] if cnn is None else list(cnn)
+        if cnn[0] != data.x.shape[1]:
+            raise ValueError(f"cnn[0] = {cnn[0]} but data.x has {data.x.shape[1]} features")
+        torch.manual_seed(seed)
+        # the first stage as `_point_cnn.yaml` / `default_ezsp.yaml` build it (and as
+        # transforms.PretrainedCNN loads it back): CNN only, no MLP, no position injection
+        self.model = PointStage(None, use_pos=False, use_diameter_parent=False, cnn_blocks=True,
+                                cnn=cnn, cnn_kernel_size=cnn_kernel_size, cnn_dilation=1,
+                                cnn_norm=GraphNorm, cnn_activation=nn.LeakyReLU(),
+                                cnn_residual=False, cnn_global_residual=False,
+                                point_mlp_on_cnn_feats=False).to(dev)
+        self.criterion = criterion.to(dev)
+        self.partition = partition
+        self.params = [p for p in self.model.parameters()]
+        parallel.broadcast_parameters(self.params, src=0)
+        self.bucket = parallel.FlatGradAllReduce(self.params)
+        self.opt = torch.optim.AdamW(self.params, lr=lr, weight_decay=weight_decay,
+                                     fused=dev.type == "cuda")
+        self.last_loss = None
+        if dev.type == "cuda":
+            _csr.edge_end_views(data.edge_index, self.n[0])     # the fixed graph: sorted once, here
+
+    @property
+    def counts(self):
+        """int64 [3] on the device: ``n_inter, n_intra, n_selected`` of the last step."""
+        return self.criterion.counts
+
+    def _forget_csr(self):
+        pass                                    # a static batch: its views stay on its tensors
+
+    def _features(self):
+        x, _ = SPT.forward_first_stage(self.data, self.model, use_node_hf=True, norm_mode="graph")
+        return x
+
+    def _fwd_bwd(self):
+        from .output import PartitionOutput
+        self.model.train()
+        self.criterion.train()
+        d = self.data
+        loss, _ = self.criterion(PartitionOutput(d.y, self._features(), d.edge_index))
+        self.bucket.zero()
+        loss.backward()
+        return loss
+
+    @torch.no_grad()
+    def evaluate(self, partition=None):
+        """Features -> ``transforms.GreedyContourPriorPartition`` (``partition``, else the one
+        given at construction) -> the oracle purity of the superpoints
+        (``validation_step_update_metrics``, src/models/semantic.py:1641-1647): the confusion
+        matrix of ``argmax(y_superpoint[:, :C])`` against ``y_superpoint``.  Returns ``(loss,
+        confusion_matrix, n_superpoints, n_points)``; the loss is the criterion's in eval mode
+        (every kept edge, no sample)."""
+        from .metrics import ConfusionMatrix
+        from .output import PartitionOutput
+        partition = partition if partition is not None else self.partition
+        if partition is None:
+            raise ValueError("evaluate() needs a partition transform (GreedyContourPriorPartition)")
+        was = self.model.training, self.criterion.training
+        self.model.eval()
+        self.criterion.eval()
+        try:
+            from .data import Data
+            src = self.data
+            d = Data(pos=src.pos, x=self._features(), edge_index=src.edge_index, y=src.y)
+            nag = partition(d)                  # (writes super_index / edge_attr on `d` only)
+            out = PartitionOutput(d.y, d.x, d.edge_index, partition=nag[1])
+            loss, out = self.criterion(out)
+        finally:
+            self.model.train(was[0])
+            self.criterion.train(was[1])
+        c = self.criterion.num_classes
+        cm = ConfusionMatrix(c, device=self.dev)
+        y_sp = out.y_superpoint
+        cm.update(y_sp[:, :c].argmax(dim=1), y_sp)
+        return loss, cm, y_sp.shape[0], d.x.shape[0]
+
+    def roofline(self, peak_gbs):
+        raise NotImplementedError("no traffic model of the partition stage")
+
+    northstar = roofline
+
+    def describe(self, scene, sizes, graph="knn"):
+        return (f"{self.name}; {self.n[0]} voxels, {self.data.edge_index.shape[1]} edges "
+                f"({graph}), {scene}")
+
+
 class ScatterChain:
     name = "segment-CSR scatter chain (CSR build + max-pool fwd/bwd over L0->L1->L2 + unpool fwd/bwd)"
     workload, k_timers, _timed_steps = None, None, 0

@@ -229,6 +229,28 @@ class UpNFuseStage(Stage):
                                num_graphs=num_graphs, ea_grad=ea_grad)
 
 
+_MAPS_ATTR = "_spt_kernel_maps"
+
+
+def _kernel_maps_of(coords, batch):
+    """The ``(kernel_size, dilation) -> KernelMap`` cache of one batch's voxels, memoised on the
+    ``coords`` tensor object like the CSR views on their index tensors (``csr.csr_of``): a map is
+    two host reads, and the voxels of a batch do not change between the steps taken on it.  The
+    key holds the versions and addresses of ``coords`` and ``batch``, so an in-place edit or
+    another batch vector starts a fresh cache."""
+    key = (coords._version, coords.data_ptr(), tuple(coords.shape), coords.dtype,
+           None if batch is None else (batch._version, batch.data_ptr(), batch.numel(), batch.dtype))
+    memo = getattr(coords, _MAPS_ATTR, None)
+    if memo is not None and memo[0] == key:
+        return memo[1]
+    maps = {}
+    try:
+        setattr(coords, _MAPS_ATTR, (key, maps))
+    except Exception:                                # a tensor that refuses attributes: no cache
+        pass
+    return maps
+
+
 class PointStage(Stage):
     """Level-0 stage: position injection + point MLP, no attention (stage.py:574-806).
     ``cnn_blocks=True`` puts the sparse CNN of EZ-SP (``nn.sparse.SparseCNN`` over the integer
@@ -273,10 +295,11 @@ class PointStage(Stage):
         from .sparse import SparseTensor
         if coords is None:
             raise ValueError("cnn_blocks=True needs the integer voxel `coords` of the points")
+        maps = _kernel_maps_of(coords, batch)
         if batch is None:
             batch = torch.zeros(coords.shape[0], dtype=coords.dtype, device=coords.device)
         coords = torch.cat([batch.view(-1, 1).to(coords.dtype), coords], dim=1)
-        x = self.cnn_blocks(SparseTensor(coords=coords, feats=x), batch=norm_index).F
+        x = self.cnn_blocks(SparseTensor(coords=coords, feats=x, maps=maps), batch=norm_index).F
         if self.point_mlp_on_cnn_feats:
             # the MLP's output is the stage's output: the pool-fused route stays correct
             x = self.feature_fusion(x, x_mlp) if x_mlp is not None else x

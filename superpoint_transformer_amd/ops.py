@@ -447,15 +447,33 @@ class _GraphNorm(torch.autograd.Function):
         return gx.to(in_dtype), None, None, gw, gb, ga, None, None
 
 
+_NGRAPHS_ATTR = "_spt_num_graphs"
+
+
+def _num_graphs_of(batch):
+    """``batch.max() + 1``, read back once per batch vector (memoised on the tensor object, keyed
+    on its version like the CSR views; ``csr.forget`` drops it)."""
+    key = (batch._version, batch.data_ptr(), batch.numel())
+    memo = getattr(batch, _NGRAPHS_ATTR, None)
+    if memo is not None and memo[0] == key:
+        return memo[1]
+    n = int(batch.max().item()) + 1 if batch.numel() else 1
+    try:
+        setattr(batch, _NGRAPHS_ATTR, (key, n))
+    except Exception:
+        pass
+    return n
+
+
 def graph_norm(x, batch, weight, bias, mean_scale, eps=1e-5, num_graphs=None,
                act_slope=1.0):
     """GraphNorm(x, batch) [+ LeakyReLU(act_slope) when act_slope != 1].
-    ``num_graphs=None`` costs a host sync (``batch.max()+1``) exactly like
+    ``num_graphs=None`` costs a host sync (``batch.max()+1``, once per batch vector) like
     PyG's GraphNorm; pass it to stay asynchronous."""
     if batch is None:
         num_graphs = 1
     elif num_graphs is None:
-        num_graphs = int(batch.max().item()) + 1 if batch.numel() else 1
+        num_graphs = _num_graphs_of(batch)
     return _GraphNorm.apply(x, batch, int(num_graphs), weight, bias, mean_scale,
                             float(eps), float(act_slope))
 
@@ -1689,6 +1707,242 @@ def edge_affinity_loss(logits, target, edge_index, node_void, node_obj, node_y, 
         return _EdgeAffinityLoss.apply(logits, target.detach(), ei, void, obj, y, cw, pw, stats,
                                        status)
     return _EdgeAffinityLossTorch.apply(logits, target, ei, void, obj, y, cw, pw, stats, status)
+
+
+# ---------------------------------------------------------------------------
+# Edge-contrast focal loss of the partition training stage (csrc/partition_loss.hip): node labels,
+# edge classes, the adaptive sample and the loss on the device; the backward walks CSR runs
+# ---------------------------------------------------------------------------
+_M64 = (1 << 64) - 1
+PARTITION_STATUS_CLAMPED = 1      # status[1]: the sample wanted more intra edges than there are
+
+
+def _rand32_int(seed, i):
+    """``rand32`` of csrc/rng.hpp in Python integers."""
+    z = (seed + 0x9E3779B97F4A7C15 * (i + 1)) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    z = z ^ (z >> 31)
+    return z >> 32
+
+
+def partition_call_seed(seed, calls):
+    """The stream of call number ``calls`` of a ``(seed, calls)`` state (``pl_call_seed``)."""
+    mask = (_rand32_int(0x5EED, 2 * calls) << 32) | _rand32_int(0x5EED, 2 * calls + 1)
+    return ((seed & _M64) ^ mask) & _M64
+
+
+def _i64c(v):
+    v &= _M64
+    return v - (1 << 64) if v >= (1 << 63) else v
+
+
+def _rand32_torch(seed, n, device):
+    """``rand32(seed, 0 .. n - 1)`` as int64 values in [0, 2**32): int64 products wrap like the
+    kernels' uint64 ones, the logical shifts are masked arithmetic ones."""
+    def lsr(z, k):
+        return (z >> k) & ((1 << (64 - k)) - 1)
+    i = torch.arange(1, n + 1, dtype=torch.int64, device=device)
+    z = i * _i64c(0x9E3779B97F4A7C15) + _i64c(seed)
+    z = (z ^ lsr(z, 30)) * _i64c(0xBF58476D1CE4E5B9)
+    z = (z ^ lsr(z, 27)) * _i64c(0x94D049BB133111EB)
+    z = z ^ lsr(z, 31)
+    return lsr(z, 32)
+
+
+def _partition_edge_loss_torch(x, y, ei, c, temperature, gamma, weight, epsilon, ratio, state,
+                               counts, status, selected):
+    """The kernels' rules as a torch composition (CPU tensors): the same decisions and the same
+    sample; the terms in float64 under autograd, whose ``norm`` backward is 0 at distance 0."""
+    n, e = x.shape[0], ei.shape[1]
+    if y.dim() == 1:
+        label = torch.where((y >= 0) & (y < c), y.long(), torch.full_like(y.long(), -1))
+    else:
+        best, label = y[:, :c].long().max(dim=1)
+        first = (y[:, :c].long() == best[:, None]).int().argmax(dim=1)   # ties to the lowest label
+        label = torch.where(best == 0, torch.full_like(first, -1), first)
+    i, j = ei[0], ei[1]
+    ok = (i >= 0) & (i < n) & (j >= 0) & (j < n)
+    ic, jc = i.clamp(0, n - 1), j.clamp(0, n - 1)
+    kept = ok & (i != j) & (label[ic] >= 0) & (label[jc] >= 0)
+    intra = kept & (label[ic] == label[jc])
+    inter = kept & ~intra
+    n_inter, n_intra = int(inter.sum()), int(intra.sum())
+    clamped = 0
+    sel = kept
+    if ratio is not None:
+        fr = torch.tensor(1.0 / ratio - 1.0, dtype=torch.float32)
+        n_major = int((torch.tensor(n_inter, dtype=torch.float32) * fr).long())
+        if n_major > n_intra:
+            n_major, clamped = n_intra, 1
+        n_major = max(n_major, 0)
+        seed = partition_call_seed(int(state[0]), int(state[1]))
+        draw = _rand32_torch(seed, e, ei.device)
+        draw = torch.where(intra, draw, torch.full_like(draw, 1 << 40))
+        order = torch.sort(draw, stable=True).indices[:n_major]      # ties to the lower position
+        sel = inter.clone()
+        sel[order] = True
+        state[1] += 1
+    else:
+        n_major = n_intra
+    n_sel = n_inter + n_major
+    if counts is not None:
+        counts.copy_(torch.tensor([n_inter, n_intra, n_sel], dtype=torch.int64))
+    if status is not None:
+        status[0] += int((~ok).sum())
+        status[1] |= clamped
+    if selected is not None:
+        selected.copy_(sel.to(selected.dtype))
+    if n_inter == 0 or n_sel == 0:
+        return (x * 0).sum()                       # exactly 0, an all-zero gradient
+    idx = sel.nonzero()[:, 0]
+    t = intra[idx]
+    xd = x.double()
+    d = (xd[i[idx]] - xd[j[idx]]).norm(dim=1)
+    p = torch.exp(-d / temperature)
+    q = torch.where(t, p, 1 - p)
+    qp = epsilon + (1 - 2 * epsilon) * q
+    w = torch.where(t, torch.full_like(qp, weight), torch.full_like(qp, 1 - weight))
+    mod = torch.ones_like(qp) if gamma == 0 else (1 - qp) ** gamma
+    return ((-w * mod * torch.log(qp)).sum() / n_sel).to(x.dtype)
+
+
+class _PartitionEdgeLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, ei, holder, c, params, ratio, state, counts, status, selected):
+        xs = x.detach()
+        if xs.dtype != torch.float32:
+            xs = xs.float()
+        n, d = xs.shape
+        if xs.stride(1) != 1 or (n > 1 and xs.stride(0) < d) or xs.data_ptr() % 4:
+            xs = xs.contiguous()
+        ldx = xs.stride(0) if n > 1 else d
+        e = ei.shape[1]
+        dev = xs.device
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        den = torch.empty(1, dtype=torch.float64, device=dev)
+        code = torch.empty(e, dtype=torch.uint8, device=dev)
+        nbytes = _lib.lib.spt_partition_loss_workspace_bytes(n, e)
+        ws = _workspace(nbytes, dev)
+        with torch.cuda.device(dev):
+            st = _lib.lib.spt_partition_loss_fwd_f32(
+                _lib.ptr(xs), ldx, n, d, _lib.ptr(y), y.shape[1] if y.dim() == 2 else 0, c,
+                _lib.ptr(ei), e, *params, -1.0 if ratio is None else float(ratio), _lib.ptr(state),
+                _lib.ptr(loss), _lib.ptr(den), _lib.ptr(code), _lib.ptr(counts), _lib.ptr(status),
+                _lib.ptr(selected), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
+        _lib.check(st, "spt_partition_loss_fwd_f32")
+        ctx.save_for_backward(xs, ei, code, den)
+        ctx.meta = (x.dtype, ldx, params, holder)
+        return loss[0].to(x.dtype)
+
+    @staticmethod
+    def backward(ctx, gout):
+        from .csr import edge_end_views
+        xs, ei, code, den = ctx.saved_tensors
+        dtype, ldx, params, holder = ctx.meta
+        n, d = xs.shape
+        e = ei.shape[1]
+        dev = xs.device
+        by_src, by_tgt = edge_end_views(holder[0], n)     # memoised on the caller's edge_index
+        g = _dense(gout.detach().reshape(1), torch.float32, 4)
+        gx = torch.empty((n, d), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            st = _lib.lib.spt_partition_loss_bwd_f32(
+                _lib.ptr(xs), ldx, n, d, _lib.ptr(ei), e, _lib.ptr(code), _lib.ptr(by_src.rowptr),
+                _lib.ptr(by_src.perm), _lib.ptr(by_tgt.rowptr), _lib.ptr(by_tgt.perm), *params,
+                _lib.ptr(g), _lib.ptr(den), _lib.ptr(gx), d, _lib.stream_ptr(dev))
+        _lib.check(st, "spt_partition_loss_bwd_f32")
+        return (gx.to(dtype),) + (None,) * 10
+
+
+def partition_edge_loss(x, y, edge_index, num_classes, temperature=1, gamma=0, weight=0.5,
+                        epsilon=1e-6, ratio=None, state=None, counts=None, status=None,
+                        selected=None):
+    """The loss of the partition training stage (``PartitionCriterion.edge_classification_loss``
+    with ``BinaryFocalLoss``, src/loss/partition_criterion.py:92-145, src/loss/focal.py:194-220),
+    differentiable in ``x`` f32 ``[N, D]`` (``D <= 128``; any row stride).
+
+    ``y``: int label histograms ``[N, num_classes + 1]`` (the node's label is the first maximum of
+    the class columns; a node whose maximum is 0 is void) or an int label vector ``[N]`` with
+    ``num_classes`` (or anything outside ``[0, num_classes)``) for void.  ``edge_index`` int
+    ``[2, E]`` in any order.  Self loops and edges with a void end are dropped; the others are
+    intra (same label, target affinity 1) or inter (0).  Per selected edge the affinity
+    ``exp(-|x_i - x_j| / temperature)`` enters the binary focal loss (``gamma``, ``weight`` of the
+    intra class, ``epsilon``); the result is the mean over the selected edges, exactly 0 (with an
+    all-zero gradient) when nothing is selected or there is no inter edge.
+
+    ``ratio`` (``adaptive_sampling_ratio``; None: every kept edge is selected): all inter edges
+    and ``int(f32(n_inter) * f32(1 / ratio - 1))`` intra edges, drawn on the device from
+    ``state``, an int64 ``[2]`` tensor ``(seed, calls)`` on ``x``'s device whose second entry the
+    call advances: the same state gives the same sample, a replayed graph draws a fresh one each
+    time.  Without a ``state`` the call draws from ``(0, 0)``.
+
+    ``counts``: optional int64 ``[3]`` buffer, WRITTEN with ``n_inter, n_intra, n_selected``.
+    ``status``: optional int32 ``[2]`` buffer; ``[0] +=`` the edges with an end outside
+    ``[0, N)`` (dropped), ``[1] |= PARTITION_STATUS_CLAMPED`` where the reference would have
+    asserted (fewer intra edges than the sample asks for: all are taken).  ``selected``: optional
+    uint8 ``[E]`` output, 1 for a selected edge.
+
+    CUDA tensors run on the HIP kernels with no host synchronisation (the call can be captured
+    into a graph) and bitwise reproducibly - the backward sums per node over the by-source and
+    by-target views of ``edge_index`` (``csr.edge_end_views``, sorted once per edge list) instead
+    of scattering with atomics; CPU tensors take a torch composition of the same rules."""
+    if x.dim() != 2 or not x.is_floating_point():
+        raise ValueError(f"x must be a floating [N, D] tensor, got {tuple(x.shape)}")
+    n, d = x.shape
+    if d < 1 or d > 128:
+        raise ValueError(f"rows of 1 to 128 features are supported, got {d}")
+    c = int(num_classes)
+    if c < 1:
+        raise ValueError("num_classes must be positive")
+    if y.is_floating_point() or y.dtype == torch.bool or y.dim() not in (1, 2) or y.shape[0] != n \
+            or (y.dim() == 2 and y.shape[1] < c):
+        raise ValueError(f"y must be an integer [{n}] label vector or [{n}, >= {c}] histogram, "
+                         f"got {tuple(y.shape)} {y.dtype}")
+    if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_index.is_floating_point():
+        raise ValueError(f"edge_index must be an integer [2, E] tensor, got {tuple(edge_index.shape)}")
+    e = edge_index.shape[1]
+    temperature, gamma, weight, epsilon = (float(temperature), float(gamma), float(weight),
+                                           float(epsilon))
+    if not temperature > 0 or not gamma >= 0 or not 0 <= weight <= 1 or not 0 <= epsilon < 0.5:
+        raise ValueError("temperature > 0, gamma >= 0, weight in [0, 1] and epsilon in [0, 0.5) "
+                         f"are needed, got {temperature}, {gamma}, {weight}, {epsilon}")
+    if ratio is not None and not 0 < float(ratio) <= 1:
+        raise ValueError(f"ratio must lie in (0, 1] or be None, got {ratio}")
+    dev = x.device
+    for name, t in (("y", y), ("edge_index", edge_index), ("state", state), ("counts", counts),
+                    ("status", status), ("selected", selected)):
+        if t is not None and t.device != dev:
+            raise ValueError(f"{name} lives on {t.device}, x on {dev}")
+    if state is not None and (state.dtype != torch.int64 or tuple(state.shape) != (2,)
+                              or not state.is_contiguous()):
+        raise ValueError("state must be a contiguous int64 [2] tensor (seed, calls)")
+    if counts is not None and (counts.dtype != torch.int64 or tuple(counts.shape) != (3,)
+                               or not counts.is_contiguous()):
+        raise ValueError("counts must be a contiguous int64 [3] tensor")
+    if status is not None and (status.dtype != torch.int32 or tuple(status.shape) != (2,)
+                               or not status.is_contiguous()):
+        raise ValueError("status must be a contiguous int32 [2] tensor")
+    if selected is not None and (selected.dtype != torch.uint8 or tuple(selected.shape) != (e,)
+                                 or not selected.is_contiguous()):
+        raise ValueError(f"selected must be a contiguous uint8 [{e}] tensor")
+    if e == 0:
+        raise ValueError("No edges found in batch.")
+    if n >= 1 << 31 or e >= 1 << 31:
+        raise ValueError("more than 2^31 - 1 nodes or edges")
+    if ratio is not None and state is None:
+        state = torch.zeros(2, dtype=torch.int64, device=dev)
+    if ratio is None:
+        state = None
+    ratio = None if ratio is None else float(ratio)
+    if not x.is_cuda:
+        return _partition_edge_loss_torch(x, y.detach(), edge_index.detach().long(), c, temperature,
+                                          gamma, weight, epsilon, ratio, state, counts, status,
+                                          selected)
+    ei = _dense(edge_index.detach(), torch.int64, 8)
+    yd = _dense(y.detach(), torch.int64, 8)
+    return _PartitionEdgeLoss.apply(x, yd, ei, (edge_index,), c, (temperature, gamma, weight, epsilon),
+                                    ratio, state, counts, status, selected)
 
 
 # ---------------------------------------------------------------------------

@@ -15,7 +15,8 @@ import torch
 
 from . import ops, predict
 
-__all__ = ["SemanticSegmentationOutput", "MultiRunInference", "PanopticSegmentationOutput"]
+__all__ = ["SemanticSegmentationOutput", "MultiRunInference", "PanopticSegmentationOutput",
+           "PartitionOutput"]
 
 log = logging.getLogger(__name__)
 
@@ -455,3 +456,31 @@ class PanopticSegmentationOutput(SemanticSegmentationOutput):
         raw_index = predict.labels_through(self.obj_index_pred, hops, want=("raw",),
                                            check=check)["raw"]
         return raw_y, raw_index, self._per_point(raw_index, raw_y)
+
+
+class PartitionOutput:
+    """What the model hands to ``criterion.PartitionCriterion`` while the partition is trained
+    (``PartitionOutput``, src/utils/output_partition.py): the nodes' labels ``y`` (int histograms
+    ``[n, C + 1]`` or labels ``[n]``), their features ``x`` ``[n, D]`` and the graph
+    ``edge_index`` ``[2, E]`` the loss contrasts them along; any further keyword becomes an
+    attribute.  With a ``partition`` attribute (the level-1 ``Data`` computed from ``x`` in
+    evaluation), ``y_superpoint`` and ``superpoint_size_histogram()`` read it."""
+
+    def __init__(self, y, x=None, edge_index=None, **kwargs):
+        self.y = y
+        self.x = x
+        self.edge_index = edge_index
+        for k, v in kwargs.items():
+            setattr(self, k, v)
+
+    @property
+    def y_superpoint(self):
+        return self.partition.y
+
+    def superpoint_size_histogram(self):
+        """``bincount`` of the superpoints' sizes."""
+        return torch.bincount(self.partition.sub.sizes)
+
+    @property
+    def has_target(self):
+        return self.y is not None

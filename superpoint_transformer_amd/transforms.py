@@ -16,7 +16,8 @@ __all__ = ["horizontal_edge_features", "EDGE_FEATURE_COLUMNS", "NodeSize", "Samp
            "NAGColorAutoContrast", "NAGColorDrop", "GeometricAugmentation", "FeatureAugmentation",
            "ColorAugmentation", "GridSampling3D", "SaveNodeIndex", "NAGSaveNodeIndex", "DataTo",
            "NAGRemoveKeys", "SegmentFeatures", "RadiusHorizontalGraph",
-           "GreedyContourPriorPartition", "QuantizePointCoordinates", "PretrainedCNN"]
+           "GreedyContourPriorPartition", "QuantizePointCoordinates", "PretrainedCNN", "KNN",
+           "AdjacencyGraph", "RemoveKeys"]
 
 EDGE_FEATURE_COLUMNS = [
     "mean_off_x", "mean_off_y", "mean_off_z", "std_off_x", "std_off_y", "std_off_z",
@@ -404,6 +405,80 @@ class AddKeysTo:
     def __call__(self, data):
         data.add_keys_to(keys=self.keys, to=self.to, strict=self.strict,
                          delete_after=self.delete_after)
+        return data
+
+
+class RemoveKeys:
+    """``RemoveKeys`` (src/transforms/data.py:154-177): drops the attributes ``keys`` from a
+    ``Data``; ``strict`` raises on a missing key.  The partition stage's chain ends with it
+    (``edge_attr``, ``neighbor_index``, ``neighbor_distance``: the loss reads ``edge_index``
+    alone)."""
+
+    def __init__(self, keys=None, strict=False):
+        from .features import sanitize_keys
+        self.keys, self.strict = sanitize_keys(keys, default=()), strict
+
+    def __call__(self, data):
+        for k in self.keys:
+            if k not in data and self.strict:
+                raise Exception(f"key: {k} is not within Data keys: {set(data.keys)}")
+        for k in self.keys:
+            data[k] = None
+        return data
+
+
+class KNN:
+    """``KNN`` (src/transforms/neighbors.py:11-88): the ``k`` nearest other points within
+    ``r_max`` of every point (``neighbors.knn_1``, per cloud of a batch) into
+    ``data.neighbor_index`` (-1: missing) and ``data.neighbor_distance``.  ``r_max <= 0`` or
+    ``k <= 0`` skips the step.  ``save_as_csr=True`` (a ``CSRData`` of the found neighbours) is
+    not built."""
+
+    def __init__(self, k=50, r_max=1, oversample=False, self_is_neighbor=False, verbose=False,
+                 save_as_csr=False):
+        if save_as_csr:
+            raise NotImplementedError("KNN(save_as_csr=True) is not supported: the neighbours stay "
+                                      "dense [N, k] with -1 for a missing one")
+        self.k, self.r_max, self.oversample = k, r_max, oversample
+        self.self_is_neighbor, self.verbose, self.save_as_csr = self_is_neighbor, verbose, save_as_csr
+
+    def __call__(self, data):
+        if self.r_max <= 0 or self.k <= 0:
+            return data
+        from .neighbors import knn_1
+        data.neighbor_index, data.neighbor_distance = knn_1(
+            data.pos, self.k, r_max=self.r_max, batch=data.get("batch"), oversample=self.oversample,
+            self_is_neighbor=self.self_is_neighbor)
+        return data
+
+
+class AdjacencyGraph:
+    """``AdjacencyGraph`` (src/transforms/graph.py:45-96): the directed, untrimmed edge list
+    ``(i, neighbor_index[i, j])`` for ``j < k`` in row order, without the missing (-1) neighbours,
+    into ``data.edge_index``; ``data.edge_attr`` is 1 for ``w <= 0``, else
+    ``1 / (w + distance / mean distance)``.  This is the graph ``criterion.PartitionCriterion``
+    contrasts the features along and the partition reads its contour prior from."""
+
+    def __init__(self, k=10, w=-1):
+        self.k, self.w = k, w
+
+    def __call__(self, data):
+        nn = data.get("neighbor_index")
+        assert nn is not None, \
+            "Data must have 'neighbor_index' attribute to allow adjacency graph construction."
+        assert data.get("neighbor_distance") is not None or self.w <= 0, \
+            "Data must have 'neighbor_distance' attribute to allow adjacency graph construction."
+        assert self.k <= nn.shape[1]
+        source = torch.arange(nn.shape[0], device=nn.device).repeat_interleave(self.k)
+        target = nn[:, :self.k].flatten()
+        mask = target >= 0
+        source, target = source[mask], target[mask]
+        data.edge_index = torch.stack((source, target))
+        if self.w > 0:
+            distances = data.neighbor_distance[:, :self.k].flatten()[mask]
+            data.edge_attr = 1 / (self.w + distances / distances.mean())
+        else:
+            data.edge_attr = torch.ones_like(source, dtype=torch.float)
         return data
 
 
