@@ -37,14 +37,16 @@ __global__ __launch_bounds__(CE_BLOCK) void ce_fwd_kernel(
     float z = 0.f;
 #pragma unroll
     for (int c = 0; c < CMAX; ++c) z += (c < C) ? expf(v[c] - m) : 0.f;
-    const float l = m + logf(z);
-    lse[row] = l;
+    const float lz = logf(z);
+    lse[row] = m + lz;
     const int64_t t = target[row];
     if (t != ignore_index && t >= 0 && t < C) {
       float picked = 0.f;
 #pragma unroll
       for (int c = 0; c < CMAX; ++c) picked = (c == (int)t) ? v[c] : picked;
-      li = (double)(l - picked);
+      // log z + (m - picked) in f64, as hl_fwd_kernel: the f32 sum m + log z carries ulp(|lse|),
+      // which at logits near -3e4 is 2e-3 on a term of order 1
+      li = (double)lz + ((double)m - (double)picked);
       ci = 1.0;
     } else if (t != ignore_index) {
       // a label outside [0, C) that is not ignore_index is a bug upstream (wrong num_classes,
@@ -106,22 +108,40 @@ __global__ __launch_bounds__(256) void ce_finish_kernel(const double* __restrict
 
 template <int CMAX>
 __global__ __launch_bounds__(CE_BLOCK) void ce_bwd_kernel(
-    const float* __restrict__ logits, const int64_t* __restrict__ target,
-    const float* __restrict__ lse, int64_t rows, int C, int64_t ignore_index,
-    const float* __restrict__ gout, const float* __restrict__ count, float* __restrict__ glogits) {
+    const float* __restrict__ logits, const int64_t* __restrict__ target, int64_t rows, int C,
+    int64_t ignore_index, const float* __restrict__ gout, const float* __restrict__ count,
+    float* __restrict__ glogits) {
   const int64_t row = (int64_t)blockIdx.x * CE_BLOCK + threadIdx.x;
   if (row >= rows) return;
-  const float scale = gout[0] / count[0];
   const int64_t t = target[row];
   const bool valid = t != ignore_index && t >= 0 && t < C;
-  const float l = lse[row];
+  if (!valid) {                                // an explicit 0, whatever the row's logits hold
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c)
+      if (c < C) glogits[row * C + c] = 0.f;
+    return;
+  }
+  // the softmax from the row's own max and sum, as hl_bwd_kernel (lse, an f32, is not read: its
+  // rounding is ulp(|lse|) relative on every probability of the row)
+  const double scale = (double)gout[0] / (double)count[0];
+  float e[CMAX];
+  float m = -INFINITY;
 #pragma unroll
   for (int c = 0; c < CMAX; ++c) {
-    if (c < C) {
-      const float p = expf(logits[row * C + c] - l);
-      glogits[row * C + c] = valid ? (p - ((int)t == c ? 1.f : 0.f)) * scale : 0.f;
-    }
+    e[c] = (c < C) ? logits[row * C + c] : -INFINITY;
+    m = fmaxf(m, e[c]);
   }
+  float z = 0.f;
+#pragma unroll
+  for (int c = 0; c < CMAX; ++c) {
+    e[c] = (c < C) ? expf(e[c] - m) : 0.f;
+    z += e[c];
+  }
+  const double rz = 1.0 / (double)z;
+#pragma unroll
+  for (int c = 0; c < CMAX; ++c)
+    if (c < C)
+      glogits[row * C + c] = (float)(((double)e[c] * rz - ((int)t == c ? 1.0 : 0.0)) * scale);
 }
 
 // ---- class-weighted CE on index targets, on the dominant label of a histogram, or against the
@@ -528,7 +548,8 @@ extern "C" size_t spt_cross_entropy_workspace_bytes(int64_t rows) {
 }
 
 // loss[0] = mean over the rows with target != ignore_index of (logsumexp(logits[row]) -
-// logits[row, target[row]]); lse[rows] is kept for the backward; count[0] = number of such rows.
+// logits[row, target[row]]); lse[rows] = the rows' f32 log-sum-exp (written as the entry promises;
+// the backward takes it and does not read it); count[0] = number of such rows.
 extern "C" int spt_cross_entropy_fwd_f32(const float* logits, const int64_t* target, int64_t rows,
                                          int C, int64_t ignore_index, float* lse, float* loss,
                                          float* count, void* ws, size_t ws_bytes,
@@ -559,9 +580,9 @@ extern "C" int spt_cross_entropy_bwd_f32(const float* logits, const int64_t* tar
   SPT_CHECK_ARG(logits && target && lse && gout && count && glogits, "null pointer");
   const int nblocks = (int)ceil_div(rows, (int64_t)CE_BLOCK);
   if (C <= 16)
-    ce_bwd_kernel<16><<<nblocks, CE_BLOCK, 0, stream>>>(logits, target, lse, rows, C, ignore_index, gout, count, glogits);
+    ce_bwd_kernel<16><<<nblocks, CE_BLOCK, 0, stream>>>(logits, target, rows, C, ignore_index, gout, count, glogits);
   else
-    ce_bwd_kernel<32><<<nblocks, CE_BLOCK, 0, stream>>>(logits, target, lse, rows, C, ignore_index, gout, count, glogits);
+    ce_bwd_kernel<32><<<nblocks, CE_BLOCK, 0, stream>>>(logits, target, rows, C, ignore_index, gout, count, glogits);
   SPT_CHECK_LAUNCH();
   return 0;
 }
